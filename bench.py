@@ -1,6 +1,13 @@
 """OAC gradient-step benchmark on MI355X (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the headline
+line; --dump-outputs DIR also writes the trained state the last timed step
+left as DIR/<name>.npy.  --full adds every other leg to the line: per-kernel
+timing and rooflines, batch 4096, the data-parallel, exploration, P-OAC and
+recipe legs, and the CPU baselines.
 
 Workload (BASELINE.json configs[1], the metric's config): SAC/OAC trainer
 step, Humanoid-v2 dims (obs 376, act 17), 2x256 MLPs, batch 256 per rank,
@@ -85,6 +92,14 @@ def parse():
     ap.add_argument("--act-dim", type=int, default=17)
     ap.add_argument("--hidden", type=int, default=256)
     ap.add_argument("--replay", type=int, default=1_000_000)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: per-kernel timing and rooflines, the batch-4096, "
+                         "data-parallel, exploration, P-OAC and recipe legs and the CPU "
+                         "baselines (--no-extras / --no-cpu-baseline trim these)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step left (parameters, targets, gradients, "
+                         "Adam moments, alpha state, the step's Q / target / log-pi rows) as "
+                         "DIR/<name>.npy, float32")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-pin", action="store_true",
                     help="leave the host threads unpinned (bench.py pins each rank to 4 cores)")
@@ -739,6 +754,29 @@ def load_traffic(B):
         return None
 
 
+def dump_outputs(tr, path):
+    """--dump-outputs: what a caller of the timed path holds after its last
+    step -- the arenas train() updates in place (get_snapshot's tensors), the
+    step's gradients and the rows get_diagnostics reads -- one float32 .npy
+    each.  The inputs are seeded (weights, replay rows, index and eps
+    streams), so two builds run with the same arguments compare file for
+    file."""
+    os.makedirs(path, exist_ok=True)
+    torch.cuda.synchronize()
+    arrays = {"params": tr.params, "targets": tr.targets, "grads": tr.grads,
+              "adam_m": tr.adam_m, "adam_v": tr.adam_v, "alpha_state": tr.alpha_state}
+    views = tr._last_plan.views
+    for k in ("q1", "q2", "y", "logp1"):
+        if k in views:
+            arrays["step_" + k] = views[k]
+    total = 0
+    for name, t in arrays.items():
+        a = np.ascontiguousarray(t.detach().to("cpu", torch.float32).numpy())
+        total += a.nbytes
+        np.save(os.path.join(path, name + ".npy"), a)
+    assert total <= 64 << 20, f"--dump-outputs wrote {total} bytes"
+
+
 def _free_port():
     import socket
     s = socket.socket()
@@ -939,23 +977,27 @@ def main():
     value = world * args.steps / elapsed
     # sanity: the trained state is finite
     assert torch.isfinite(tr.params).all().item(), "non-finite parameters"
+    if args.dump_outputs and rank == 0:
+        dump_outputs(tr, args.dump_outputs)
 
-    kt = kernel_timing(tr, rb, B, args.timing_steps)   # every rank steps (collectives)
+    # every rank steps (collectives)
+    kt = kernel_timing(tr, rb, B, args.timing_steps) if args.full else None
     # configs[2] (N = 1) / configs[3] (N > 1): the same trainer at batch 4096 per rank
     big = None
-    if not args.no_extras and B != 4096:
+    if args.full and not args.no_extras and B != 4096:
         big = batch_leg("SAC/OAC trainer step, Humanoid-v2 dims, 2x256, batch 4096 per rank, "
                         "replay 1e6 (BASELINE configs[%d])" % (3 if world > 1 else 2),
                         tr, rb, 4096, 320, 32, FLOP_PER_SAMPLE, world, device, rank=rank,
                         exec_flop_per_sample=EXEC_FLOP_PER_SAMPLE)
     out = None
-    if rank == 0:
+    if rank == 0 and args.full:
         roof = roofline_of(kt, FLOP_PER_SAMPLE, B, args.timing_steps,
                            exec_flop_per_sample=EXEC_FLOP_PER_SAMPLE)
         # B >= 1024: per-launch choice among gemm_fwd_kernel (forward),
         # gemm_bwdp_kernel (backward) and gemm_small_kernel (narrow products)
         roof["kernel"] = ("gemm_small_kernel" if B < 1024 else
                           "gemm launches (gemm_fwd / gemm_bwdp / gemm_small)")
+    if rank == 0:
         out = {
             "metric": "OAC gradient steps/sec, Humanoid-v2 dims, batch 256, 1->8 MI355X",
             "value": round(value, 2),
@@ -975,12 +1017,13 @@ def main():
                                 "train_from_ring, %d steps per graph launch" % n)},
             "samples_per_s": round(value * B, 1),
             "mode": args.mode,
-            "roofline": roof,
             "step_roofline_frac": round(FLOP_PER_SAMPLE * B * value / world / 1e12
                                         / PEAK_FP32_TFLOPS, 5),
-            "kernels": {k: {kk: round(vv, 4) if isinstance(vv, float) else vv
-                            for kk, vv in v.items()} for k, v in kt.items()},
         }
+    if rank == 0 and args.full:
+        out["roofline"] = roof
+        out["kernels"] = {k: {kk: round(vv, 4) if isinstance(vv, float) else vv
+                              for kk, vv in v.items()} for k, v in kt.items()}
         if big is not None:
             out["b4096"] = big
         out.update(hbm_legs(kt, B, args.timing_steps))
@@ -1013,6 +1056,7 @@ def main():
             if "poac_ant_b4096" in out:   # configs[4]: P-OAC K=10, Ant dims, batch 4096
                 out["poac_ant_b4096"]["cpu_baseline"] = cpu_baseline_fresh(   # (~12.7 steps/s: >= 2 s runs)
                     args, steps=26, warmup=2, all_runs=0, kind="poac", B=4096, dims=[111, 8, 256])
+    if rank == 0:
         print(json.dumps(out), flush=True)
     if dp:
         # the trainer's teardown (its captured step graphs hold RCCL kernels),

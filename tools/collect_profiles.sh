@@ -5,8 +5,9 @@ set -e
 R=${1:-r04}
 D=profiles/$R
 mkdir -p $D
-tail -1 gpurun_out/bench256.log > $D/bench_default.json
-tail -1 gpurun_out/bench4096.log > $D/bench_b4096.json
+B=${BENCH_OUT:-measure_out}   # the `bench.py --full` lines of the measurement run
+tail -1 $B/bench256.log > $D/bench_default.json
+tail -1 $B/bench4096.log > $D/bench_b4096.json
 cp "$(ls -t gpurun_out/prof_b256/*/*kernel_stats.csv | head -1)" $D/b256_kernel_stats.csv
 cp "$(ls -t gpurun_out/prof_b4096/*/*kernel_stats.csv | head -1)" $D/b4096_kernel_stats.csv
 cp "$(ls -t gpurun_out/prof_poac4096/*/*kernel_stats.csv | head -1)" $D/poac4096_kernel_stats.csv

@@ -5,13 +5,15 @@
 # Outputs under gpurun_out/; copy the summaries into profiles/<round>/.
 set -o pipefail
 mkdir -p gpurun_out
-timeout -k 10 300 python bench.py > gpurun_out/bench256.log 2>&1 &&
-timeout -k 10 200 python bench.py --batch 4096 --steps 296 --warmup 32 --no-cpu-baseline > gpurun_out/bench4096.log 2>&1 &&
+B=${BENCH_OUT:-measure_out}   # where the bench lines go (tools/collect_profiles.sh reads them there)
+mkdir -p $B
+timeout -k 10 600 python bench.py --full > $B/bench256.log 2>&1 &&
+timeout -k 10 200 python bench.py --full --batch 4096 --steps 296 --warmup 32 --no-cpu-baseline > $B/bench4096.log 2>&1 &&
 bash tools/prof.sh b256 &&
 bash tools/prof.sh b4096 --batch 4096 --steps 48 --warmup 16 &&
 bash tools/pmc.sh b256 &&
 bash tools/pmc.sh b4096 --batch 4096 &&
 bash tools/pmc_poac.sh
 rc=$?
-tail -1 gpurun_out/bench256.log | cut -c1-400
+tail -1 $B/bench256.log | cut -c1-400
 exit $rc

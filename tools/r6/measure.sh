@@ -15,9 +15,9 @@ timeout -k 10 1000 python -u -m pytest tests -m gpu -x -v -s --timeout 240 --tim
 tail -1 $O/gputest_final.txt
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.txt 2>&1; crash $?
 for i in 1 2 3; do
-  timeout -k 10 300 python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_driver_shape_$i.json 2>$O/bench_driver_shape.err; crash $?
+  timeout -k 10 300 python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_driver_shape_$i.json 2>$O/bench_driver_shape.err; crash $?
   python3 -c "import json;d=json.loads(open('$O/bench_driver_shape_$i.json').read().strip().splitlines()[-1]);print('driver shape',d['value'],d['roofline']['frac'])"
 done
-timeout -k 10 500 python bench.py > $O/bench256.log 2>&1; crash $?
+timeout -k 10 500 python bench.py --full > $O/bench256.log 2>&1; crash $?
 tail -1 $O/bench256.log | cut -c1-300
-timeout -k 10 300 python bench.py --batch 4096 --steps 296 --warmup 32 --no-cpu-baseline --no-extras > $O/bench4096.log 2>&1; crash $?
+timeout -k 10 300 python bench.py --full --batch 4096 --steps 296 --warmup 32 --no-cpu-baseline --no-extras > $O/bench4096.log 2>&1; crash $?

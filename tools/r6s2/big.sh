@@ -10,5 +10,5 @@ timeout -k 10 900 python -u -m pytest tests -m gpu -x -q --timeout 240 --timeout
 tail -3 $O/tests_$TAG.txt; crash $rc
 timeout -k 10 200 python tools/launch_times.py --batch 4096 > $O/lt4096_$TAG.txt 2>&1; crash $?
 cat $O/lt4096_$TAG.txt
-timeout -k 10 300 python bench.py --batch 4096 --steps 296 --warmup 32 --no-cpu-baseline --no-extras > $O/bench4096_$TAG.json 2>$O/bench4096_$TAG.err; crash $?
+timeout -k 10 300 python bench.py --full --batch 4096 --steps 296 --warmup 32 --no-cpu-baseline --no-extras > $O/bench4096_$TAG.json 2>$O/bench4096_$TAG.err; crash $?
 python3 -c "import json;d=json.loads(open('$O/bench4096_$TAG.json').read().strip().splitlines()[-1]);print('b4096',d['value'],d['roofline']['frac'])"

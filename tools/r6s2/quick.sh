@@ -11,6 +11,6 @@ tail -3 $O/tests_$TAG.txt; crash $rc
 timeout -k 10 200 python tools/launch_times.py --batch 256 > $O/lt256_$TAG.txt 2>&1; crash $?
 cat $O/lt256_$TAG.txt
 for i in 1 2; do
-  timeout -k 10 300 python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_${TAG}_$i.json 2>$O/bench_$TAG.err; crash $?
+  timeout -k 10 300 python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_${TAG}_$i.json 2>$O/bench_$TAG.err; crash $?
   python3 -c "import json;d=json.loads(open('$O/bench_${TAG}_$i.json').read().strip().splitlines()[-1]);print('driver shape',d['value'],d['roofline']['frac'])"
 done
