@@ -22,6 +22,11 @@
  *                         (trainer/gaussian_trainer.py:177-437)
  *   OAC_KIND_PARTICLE_UB  ParticleTrainer.train_from_torch, share_layers=True
  *                         (trainer/particle_trainer.py:175-432; the p-oac recipes)
+ *   OAC_KIND_DDPG         DDPGTrainer.train_from_torch (--alg ddpg; one critic, the
+ *                         deterministic policy, optional frozen target_policy_network;
+ *                         trainer/ddpg_trainer.py:92-184)
+ *   oac_policy_eval_fixed_std   TanhGaussianPolicy.forward with a fixed std
+ *                         (trainer/policies.py:244-249, 280-282; main.py:144-149)
  *   oac_expl_action       get_optimistic_exploration_action (stochastic branch)
  *                         (optimistic_exploration.py:7-11, 14-109)
  *   oac_replay_sample_indices   np.random.randint(0, size, B) (replay_buffer.py:107)
@@ -46,14 +51,19 @@ enum oac_kind {
   OAC_KIND_SAC = 0,          /* SACTrainer (OAC / SAC)                         */
   OAC_KIND_PARTICLE = 1,     /* particle_trainer_oac.ParticleTrainer (p-oac + OAC exploration) */
   OAC_KIND_GAUSS = 2,        /* gaussian_trainer.GaussianTrainer (g-oac)       */
-  OAC_KIND_PARTICLE_UB = 3   /* particle_trainer.ParticleTrainer (p-oac recipes: deterministic
+  OAC_KIND_PARTICLE_UB = 3,  /* particle_trainer.ParticleTrainer (p-oac recipes: deterministic
                                 policy, upper-bound quantile loss, target_policy) */
+  OAC_KIND_DDPG = 4          /* ddpg_trainer.DDPGTrainer (--alg ddpg): one critic with q_out=1,
+                                deterministic policy, no target_policy block; single-process
+                                only (oac_sac_step_phase / _set_allreduce / _set_step_graph
+                                and OAC_STEP_USE_GRAPH are rejected for this kind) */
 };
 
 typedef struct oac_sac_config {
   int kind;              /* OAC_KIND_SAC (twin critics, q_out=1); OAC_KIND_PARTICLE and
                             OAC_KIND_PARTICLE_UB (one critic, q_out = K particles);
-                            OAC_KIND_GAUSS (one critic, q_out=2: mean | log std) */
+                            OAC_KIND_GAUSS (one critic, q_out=2: mean | log std);
+                            OAC_KIND_DDPG (one critic, q_out=1) */
   int obs_dim, act_dim;
   int hidden;            /* width of both hidden layers (reference: [M]*N, N=2) */
   int q_out;             /* 1 for SAC/OAC; K heads for the shared-layer particle critic */
@@ -90,7 +100,7 @@ typedef struct oac_sac_config {
  * last_fc.weight, rows Da..2Da-1 = last_fc_log_std.weight) and their biases
  * likewise.  Each critic block holds fc0.weight, fc0.bias, fc1.weight,
  * fc1.bias, last_fc.weight, last_fc.bias.  Arenas: params/grads/adam_m/adam_v
- * = [policy | critic 1 | critic 2] (one critic for PARTICLE; [policy |
+ * = [policy | critic 1 | critic 2] (one critic for PARTICLE and DDPG; [policy |
  * target_policy | critic] for GAUSS and PARTICLE_UB); targets = [target critic 1 | target
  * critic 2]. */
 typedef struct oac_sac_layout {
@@ -122,7 +132,8 @@ typedef struct oac_sac_buffers {
   int32_t* counts; int32_t* count_tags; int32_t* count_epoch;
   /* GAUSS / PARTICLE_UB with use_target_policy and no mean_update
    * (particle_trainer.py:150-154, 196-199; gaussian_trainer.py:154-158,
-   * 196-199): a policy-shaped block (layout pol_* offsets) whose actions on
+   * 196-199) and DDPG with use_target_policy (ddpg_trainer.py:66-70,
+   * 117-121): a policy-shaped block (layout pol_* offsets) whose actions on
    * next_obs replace the policy's in the TD target; NULL = the policy */
   const float* next_policy;
 } oac_sac_buffers;
@@ -141,10 +152,10 @@ enum oac_ws_buffer {
   OAC_WS_LOGP_PART,                    /* [ceil(B/16)] sum of (logp1 + target_entropy) per 16-row
                                           block: the data-parallel alpha exchange (world_size > 1)
                                           all-reduces this vector, the targets kernel sums it */
-  OAC_WS_H2Q1, OAC_WS_H2Q2,            /* SAC: the critics' second hidden layer on (obs, a) [B, H]
+  OAC_WS_H2Q1, OAC_WS_H2Q2,            /* SAC (DDPG: H2Q1): the critics' second hidden layer on (obs, a) [B, H]
                                           after the ReLU -- the masks their backward used (parity
                                           checks; 0 rows for the other kinds) */
-  OAC_WS_H1P, OAC_WS_H2P,              /* SAC / P-OAC: the policy's hidden layers on obs [B, H]
+  OAC_WS_H1P, OAC_WS_H2P,              /* SAC / P-OAC / DDPG: the policy's hidden layers on obs [B, H]
                                           after the ReLU -- the masks the policy backward used
                                           (parity checks; 0 rows for the other kinds) */
   OAC_WS_COUNT_PUBLIC
@@ -406,6 +417,17 @@ int oac_policy_eval(const float* net, const int64_t* offsets, int obs_dim, int a
                     const float* obs, int64_t ld_obs, int n, const float* eps, float* action,
                     float* mean, float* log_std, float* log_prob, float* std_out, float* pre_tanh,
                     void* stream);
+
+/* The same for a policy built with a fixed std (TanhGaussianPolicy(std=...),
+ * trainer/policies.py:244-249, 280-282; what main.py builds for --alg ddpg):
+ * std_dev [act_dim] device floats; std = std_dev and log_std = log(std_dev) in
+ * every row, the log-std head rows of the block are not read; a stochastic
+ * call samples tanh(mean + std_dev * eps). */
+int oac_policy_eval_fixed_std(const float* net, const int64_t* offsets, int obs_dim, int act_dim,
+                              int hidden, const float* obs, int64_t ld_obs, int n,
+                              const float* std_dev, const float* eps, float* action, float* mean,
+                              float* log_std, float* log_prob, float* std_out, float* pre_tanh,
+                              void* stream);
 
 /* ---------------------------------------------------------------- errors */
 const char* oac_last_error(void);

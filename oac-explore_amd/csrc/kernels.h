@@ -170,6 +170,9 @@ struct MlpEvalArgs {
   // policy outputs ([N, Q/2] each; log_prob [N] or null); eps null = deterministic
   const float* p_eps;
   float* p_action; float* p_mean; float* p_log_std; float* p_log_prob; float* p_std; float* p_pre_tanh;
+  // policy with a fixed per-dimension std [Q/2] (TanhGaussianPolicy(std=...)):
+  // the log-std head rows are not read
+  const float* p_fixed_std;
 };
 
 // ------------------------------------------------------------ replay/adam
@@ -307,6 +310,34 @@ struct DetHeadBwdArgs {                 // d tanh(mean): dmean = da (1 - a^2), d
   int nseg, B, act_dim;
 };
 hipError_t launch_det_head_backward(const DetHeadBwdArgs& a, hipStream_t s);
+
+// DDPGTrainer (trainer/ddpg_trainer.py:106-132): the three width-1 last layers
+// of the step -- Q(obs, a), Q_T(next_obs, a') and Q(obs, a~), all with
+// pre-step weights -- evaluated here (row_heads), then per row
+//   y = scale * r + (1 - d) * gamma * tq,  dq = 2 (q - y) / B  (MSE backward),
+//   gq = -1 / B  (seed of -mean(q_new)),   sqe = (q - y)^2,  qnew = q_new
+struct DdpgTargetArgs {
+  RowHead qh, th, nh;                   // h set in all three (K = 1)
+  const float* batch; long ld_batch; int off_rew, off_term;
+  float reward_scale, discount;
+  int B;
+  float* y; float* dq; float* gq; float* sqe; float* qnew;   // [B]
+};
+hipError_t launch_ddpg_targets(const DdpgTargetArgs& a, hipStream_t s);
+
+// dL/da through the critic's action columns and the deterministic head's
+// backward in one launch: dmean[r, j] = (1 - a[r, j]^2) sum_n dh1[r, n] wa[n, j]
+// (wa = W0[:, Do:], row n at wa + n * ld_wa), d raw log std = 0; with dh2 also
+// the head's dX, dh2[r, c] = [h2[r, c] > 0] sum_j dmean[r, j] wh[j, c] (wh = the
+// stacked heads [2 Da, H]: the mean rows; the log-std rows meet a zero gradient)
+struct DdpgHeadBwdArgs {
+  const float* dh1; const float* wa; long ld_wa;   // [B, H], [H, Da]
+  const float* act;                                // [B, Da] a~ = tanh(mean)
+  float* dhead;                                    // [B, 2 Da]
+  const float* wh; const float* h2; float* dh2;    // [2 Da, H], [B, H], [B, H] (dh2 null: not computed)
+  int B, H, Da;
+};
+hipError_t launch_ddpg_head_backward(const DdpgHeadBwdArgs& a, hipStream_t s);
 
 struct LogpSumArgs { const float* logp; int B; float target_entropy; AlphaState* alpha; };
 hipError_t launch_logp_sum(const LogpSumArgs& a, hipStream_t s);

@@ -109,8 +109,41 @@ __global__ void __launch_bounds__(256) policy_eval_kernel(MlpEvalArgs a) {
   const float* net = a.net[0];
   load_input(a, row, x);
   trunk(net, a, x, din, h0, h1);
-  dense_rows(net + a.wl, net + a.bl, h1, H, 2 * Da, hd, false);
+  dense_rows(net + a.wl, net + a.bl, h1, H, a.p_fixed_std ? Da : 2 * Da, hd, false);
   __syncthreads();
+  if (a.p_fixed_std) {
+    // std given (policies.py:244-249, 280-282): log_std = log(std), neither
+    // clamped; z = mean + std eps (:179-186); log-prob per dimension in double
+    // (Normal.log_prob minus log(1 - a^2 + 1e-6), :147-160), summed in order
+    double* lpd = reinterpret_cast<double*>(lds + (((din + 2 * H + 2 * Da + Da) + 1) & ~1));
+    for (int i = threadIdx.x; i < Da; i += blockDim.x) {
+      const long o = (long)row * Da + i;
+      const float mean = hd[i], sd = a.p_fixed_std[i];
+      a.p_mean[o] = mean;
+      a.p_log_std[o] = (float)log((double)sd);
+      a.p_std[o] = sd;
+      if (a.p_eps) {
+        const float z = __fadd_rn(mean, __fmul_rn(sd, a.p_eps[o]));
+        const float act = tanhf(z);
+        a.p_action[o] = act;
+        a.p_pre_tanh[o] = z;
+        const double u = (double)z - (double)mean, sdd = (double)sd, ad = (double)act;
+        lpd[i] = -(u * u) / (2.0 * sdd * sdd) - log(sdd) - 0.91893853320467274178 -
+                 log(1.0 - ad * ad + 1e-6);
+      } else {
+        a.p_action[o] = tanhf(mean);
+        a.p_pre_tanh[o] = mean;
+        lpd[i] = 0.0;
+      }
+    }
+    __syncthreads();
+    if (a.p_log_prob && threadIdx.x == 0) {
+      double sum = 0.0;
+      for (int i = 0; i < Da; ++i) sum += lpd[i];
+      a.p_log_prob[row] = (float)sum;
+    }
+    return;
+  }
   for (int i = threadIdx.x; i < Da; i += blockDim.x) {
     const long o = (long)row * Da + i;
     const float mean = hd[i];
@@ -140,7 +173,8 @@ __global__ void __launch_bounds__(256) policy_eval_kernel(MlpEvalArgs a) {
 
 size_t mlp_eval_lds_bytes(const MlpEvalArgs& a, bool policy) {
   const int din = a.d0 + a.d1;
-  return sizeof(float) * (size_t)(policy ? din + 2 * a.H + a.Q + a.Q / 2 + 4
+  // (policy: + Q doubles-as-floats for the fixed-std log-prob terms, 8-byte aligned)
+  return sizeof(float) * (size_t)(policy ? din + 2 * a.H + a.Q + a.Q / 2 + 4 + (a.p_fixed_std ? a.Q + 2 : 0)
                                          : din + 4 * a.H + a.Q + 4);
 }
 
@@ -209,6 +243,34 @@ extern "C" int oac_policy_eval(const float* net, const int64_t* offsets, int obs
   a.H = hidden; a.Q = 2 * act_dim; a.N = n;
   a.p_eps = eps; a.p_action = action; a.p_mean = mean; a.p_log_std = log_std;
   a.p_log_prob = log_prob; a.p_std = std_out; a.p_pre_tanh = pre_tanh;
+  OAC_HIP_CHECK(launch_policy_eval(a, reinterpret_cast<hipStream_t>(stream)));
+  return 0;
+}
+
+extern "C" int oac_policy_eval_fixed_std(const float* net, const int64_t* offsets, int obs_dim,
+                                         int act_dim, int hidden, const float* obs, int64_t ld_obs,
+                                         int n, const float* std_dev, const float* eps,
+                                         float* action, float* mean, float* log_std, float* log_prob,
+                                         float* std_out, float* pre_tanh, void* stream) {
+  if (!net || !offsets || obs_dim < 1 || act_dim < 1 || hidden < 1 || n < 0 || !obs || !std_dev ||
+      !action || !mean || !log_std || !std_out || !pre_tanh) {
+    set_error("policy eval (fixed std): bad arguments");
+    return 1;
+  }
+  if ((size_t)(obs_dim + 2 * hidden + 5 * act_dim + 8) * 4 > 160 * 1024) {
+    set_error("policy eval (fixed std): dims exceed the workgroup's LDS");
+    return 1;
+  }
+  MlpEvalArgs a;
+  memset(&a, 0, sizeof(a));
+  a.net[0] = net; a.n_nets = 1;
+  a.w0 = offsets[0]; a.b0 = offsets[1]; a.w1 = offsets[2]; a.b1 = offsets[3];
+  a.wl = offsets[4]; a.bl = offsets[5];
+  a.x0 = obs; a.ld_x0 = ld_obs; a.d0 = obs_dim;
+  a.H = hidden; a.Q = 2 * act_dim; a.N = n;
+  a.p_eps = eps; a.p_action = action; a.p_mean = mean; a.p_log_std = log_std;
+  a.p_log_prob = log_prob; a.p_std = std_out; a.p_pre_tanh = pre_tanh;
+  a.p_fixed_std = std_dev;
   OAC_HIP_CHECK(launch_policy_eval(a, reinterpret_cast<hipStream_t>(stream)));
   return 0;
 }

@@ -845,6 +845,100 @@ __global__ void __launch_bounds__(256) det_head_backward_kernel(DetHeadBwdArgs p
   dh[Da + j] = 0.f;
 }
 
+// --------------------------------------------------------------------------
+// DDPGTrainer (trainer/ddpg_trainer.py).  One critic with one output; all
+// three critic evaluations of the step use the pre-step weights (:106, :114,
+// :127), so their last layers run here, ahead of the critic's Adam.
+// --------------------------------------------------------------------------
+__global__ void __launch_bounds__(256) ddpg_targets_kernel(DdpgTargetArgs p) {
+  __shared__ RowHeadLds hq, ht, hn;
+  const int r0 = blockIdx.x * kRowBlock, r = r0 + threadIdx.x;
+  row_heads(p.qh, 1, p.B, r0, hq);
+  row_heads(p.th, 1, p.B, r0, ht);
+  row_heads(p.nh, 1, p.B, r0, hn);
+  __syncthreads();
+  if (threadIdx.x >= kRowBlock || r >= p.B) return;
+  const float q = hq.out[threadIdx.x][0], tq = ht.out[threadIdx.x][0];
+  const float rew = p.batch[(long)r * p.ld_batch + p.off_rew];
+  const float term = p.batch[(long)r * p.ld_batch + p.off_term];
+  const float gd = __fmul_rn(1.f - term, p.discount);                               // :129-130
+  const float y = __fadd_rn(__fmul_rn(p.reward_scale, rew), __fmul_rn(gd, tq));
+  const float invB = 1.f / (float)p.B;
+  const float d = q - y;
+  p.y[r] = y;
+  p.dq[r] = __fmul_rn(2.f * d, invB);
+  p.gq[r] = -invB;
+  p.sqe[r] = d * d;
+  p.qnew[r] = hn.out[threadIdx.x][0];
+}
+
+// one workgroup per row.  dL/da: lane = (hidden-unit phase, action dim j), so a
+// wave's load of the action columns covers two whole rows of W0[:, Do:]
+// (contiguous in j); the 8 phases (4 waves x 2 half-waves) each sum every 8th
+// hidden unit in 8 independent chains, added in a fixed order.  Then the
+// head's dX, one thread per hidden column (coalesced rows of the head).
+constexpr int kDdpgMaxDa = 32;
+__global__ void __launch_bounds__(256) ddpg_head_backward_kernel(DdpgHeadBwdArgs p) {
+  __shared__ float part[4][kDdpgMaxDa];
+  __shared__ float dm[kDdpgMaxDa];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int r = blockIdx.x;
+  const int Da = p.Da, H = p.H;
+  const int j = min(lane & 31, Da - 1);
+  const float* d = p.dh1 + (long)r * H;
+  const float* w = p.wa + j;
+  float acc[8];
+#pragma unroll
+  for (int u = 0; u < 8; ++u) acc[u] = 0.f;
+  for (int n0 = 2 * wave + (lane >> 5); n0 < H; n0 += 64) {
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const int n = n0 + 8 * u;
+      const int nc = min(n, H - 1);   // (clamped, so the loads are unpredicated)
+      const float v = d[nc] * w[(long)nc * p.ld_wa];
+      acc[u] += n < H ? v : 0.f;
+    }
+  }
+  float s = ((acc[0] + acc[1]) + (acc[2] + acc[3])) + ((acc[4] + acc[5]) + (acc[6] + acc[7]));
+  s += __shfl_xor(s, 32, 64);
+  if (lane < kDdpgMaxDa) part[wave][lane] = s;
+  __syncthreads();
+  if (threadIdx.x < kDdpgMaxDa) {
+    const int t = threadIdx.x;
+    float dmean = 0.f;
+    if (t < Da) {
+      const float da = ((part[0][t] + part[1][t]) + part[2][t]) + part[3][t];
+      const float a = p.act[(long)r * Da + t];
+      dmean = __fmul_rn(da, __fsub_rn(1.f, __fmul_rn(a, a)));   // policies.py:286-288
+      float* dh = p.dhead + (long)r * 2 * Da;
+      dh[t] = dmean;
+      dh[Da + t] = 0.f;
+    }
+    dm[t] = dmean;
+  }
+  if (!p.dh2) return;
+  __syncthreads();
+  for (int c = threadIdx.x; c < H; c += 256) {
+    float t = 0.f;
+#pragma unroll 4
+    for (int k = 0; k < Da; ++k) t = fmaf(dm[k], p.wh[(long)k * H + c], t);
+    p.dh2[(long)r * H + c] = p.h2[(long)r * H + c] > 0.f ? t : 0.f;
+  }
+}
+
+hipError_t launch_ddpg_targets(const DdpgTargetArgs& a, hipStream_t s) {
+  if (!a.qh.h || !a.th.h || !a.nh.h || !head_ok(a.qh) || !head_ok(a.th) || !head_ok(a.nh) || a.B < 1)
+    return hipErrorInvalidValue;
+  OAC_LAUNCH(ddpg_targets_kernel, dim3((a.B + kRowBlock - 1) / kRowBlock), dim3(256), 0, s, a);
+  return hipGetLastError();
+}
+hipError_t launch_ddpg_head_backward(const DdpgHeadBwdArgs& a, hipStream_t s) {
+  if (a.B < 1 || a.Da < 1 || a.Da > kDdpgMaxDa || a.H < 1 || (a.dh2 && (!a.wh || !a.h2)))
+    return hipErrorInvalidValue;
+  OAC_LAUNCH(ddpg_head_backward_kernel, dim3(a.B), dim3(256), 0, s, a);
+  return hipGetLastError();
+}
+
 hipError_t launch_gauss_targets(const GaussTargetArgs& a, hipStream_t s) {
   if (!head_ok(a.th)) return hipErrorInvalidValue;
   OAC_LAUNCH(gauss_targets_kernel, dim3((a.B + kRowBlock - 1) / kRowBlock), dim3(256), 0, s, a);

@@ -188,4 +188,11 @@ void det_layout_workspace(SacPlan& p);
 int det_run_step(SacPlan& p, int flags, hipStream_t s);
 int det_step_phase(SacPlan& p, int phase, int flags, hipStream_t s);
 
+// DDPGTrainer: one critic, deterministic policy, no target_policy block
+// (ddpg_plan.hip); single-process only
+void ddpg_layout_workspace(SacPlan& p);
+int ddpg_run_step(SacPlan& p, int flags, hipStream_t s);
+int ddpg_ws_alias(int which);   // public view id -> the DDPG layout's buffer
+int ddpg_shadow_ws();           // workspace id of its shadow weights
+
 }  // namespace oac

@@ -887,7 +887,7 @@ int oac_tuning_set(int key, int value) {
 static int validate(const oac_sac_config* c) {
   if (!c) { set_error("null config"); return 1; }
   if (c->kind != OAC_KIND_SAC && c->kind != OAC_KIND_PARTICLE && c->kind != OAC_KIND_GAUSS &&
-      c->kind != OAC_KIND_PARTICLE_UB) {
+      c->kind != OAC_KIND_PARTICLE_UB && c->kind != OAC_KIND_DDPG) {
     set_error("bad kind %d", c->kind);
     return 1;
   }
@@ -901,6 +901,14 @@ static int validate(const oac_sac_config* c) {
     return 1;
   }
   if (c->kind == OAC_KIND_SAC && c->q_out != 1) { set_error("SAC needs q_out == 1"); return 1; }
+  if (c->kind == OAC_KIND_DDPG && c->q_out != 1) {
+    set_error("DDPG (kind %d) needs q_out == 1, got %d", c->kind, c->q_out);
+    return 1;
+  }
+  if (c->kind == OAC_KIND_DDPG && c->world_size != 1) {
+    set_error("DDPG (kind %d) is single-process: world_size must be 1", c->kind);
+    return 1;
+  }
   if (c->kind == OAC_KIND_PARTICLE && (c->q_out < 1 || c->q_out > 16)) {
     set_error("particle critic: 1 <= q_out <= 16 heads");
     return 1;
@@ -978,6 +986,7 @@ int oac_sac_query_layout(const oac_sac_config* cfg, oac_sac_layout* out) {
   plan_splits(p);
   if (p.c.kind == OAC_KIND_PARTICLE) particle_layout_workspace(p);
   else if (has_target_policy(p.c.kind)) det_layout_workspace(p);
+  else if (p.c.kind == OAC_KIND_DDPG) ddpg_layout_workspace(p);
   else layout_workspace(p);
   *out = p.L;
   return 0;
@@ -993,13 +1002,16 @@ int oac_sac_create(const oac_sac_config* cfg, const oac_sac_buffers* bufs, oac_s
   plan_splits(p);
   if (p.c.kind == OAC_KIND_PARTICLE) particle_layout_workspace(p);
   else if (has_target_policy(p.c.kind)) det_layout_workspace(p);
+  else if (p.c.kind == OAC_KIND_DDPG) ddpg_layout_workspace(p);
   else layout_workspace(p);
   p.b = *bufs;
-  if (p.ws[W_QSHADOW].rows > 0 && p.b.workspace && p.b.params) {
+  const int shadow = p.c.kind == OAC_KIND_SAC ? (int)W_QSHADOW
+                     : p.c.kind == OAC_KIND_DDPG ? ddpg_shadow_ws() : -1;
+  if (shadow >= 0 && p.ws[shadow].rows > 0 && p.b.workspace && p.b.params) {
     // the shadow's float4 copies also carry the segments' al4 padding back
     // into the parameters: start it as the parameters' own
     const size_t bytes = sizeof(float) * (size_t)p.L.n_critics * p.L.q_size;
-    if (hipMemcpy(p.W(W_QSHADOW), p.b.params + p.L.q1_base, bytes, hipMemcpyDeviceToDevice) != hipSuccess) {
+    if (hipMemcpy(p.W(shadow), p.b.params + p.L.q1_base, bytes, hipMemcpyDeviceToDevice) != hipSuccess) {
       set_error("shadow init: %s", hipGetErrorString(hipGetLastError()));
       delete h;
       return 1;
@@ -1029,6 +1041,11 @@ int oac_sac_step_n(oac_sac* h, int flags, int n_steps, void* stream) {
   SacPlan& p = h->plan;
   if (n_steps < 1 || n_steps > 1024) { set_error("n_steps %d out of range", n_steps); return 1; }
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  if (p.c.kind == OAC_KIND_DDPG && (flags & OAC_STEP_USE_GRAPH)) {
+    set_error("DDPG (kind %d): OAC_STEP_USE_GRAPH is not supported, issue the step's launches "
+              "directly", p.c.kind);
+    return 1;
+  }
   if (dp_exchanges(p)) {   // the data-parallel step, exchanges through the hook (direct launches)
     for (int i = 0; i < n_steps; ++i)
       if (run_step_dp(p, flags & ~OAC_STEP_USE_GRAPH, s)) return 1;
@@ -1043,6 +1060,7 @@ int oac_sac_step_n(oac_sac* h, int flags, int n_steps, void* stream) {
     for (int i = 0; i < n_steps; ++i) {
       const int rc = p.c.kind == OAC_KIND_PARTICLE ? particle_run_step(p, f, s)
                      : has_target_policy(p.c.kind) ? det_run_step(p, f, s)
+                     : p.c.kind == OAC_KIND_DDPG   ? ddpg_run_step(p, f, s)
                                                    : run_step(p, f, s, i, n_steps);
       if (rc) return rc;
     }
@@ -1117,7 +1135,7 @@ int oac_sac_set_host_ring(oac_sac* h, int32_t* pinned_ring) {
     p.owns_host_ring = true;
     // direct mode needs the small-batch kernel (cfg 0)
     p.rows_direct = p.cfg == 0 && !has_target_policy(p.c.kind) &&
-                    p.c.kind != OAC_KIND_PARTICLE &&   // sac_plan's run_step / phase0 only
+                    p.c.kind != OAC_KIND_PARTICLE &&   // sac_plan's phase0, ddpg_plan's forward
                     p.c.row_stride / 4 <= 64 * 4;      // a side wave's row copy (gemm_small.hip)
     // (a direct large-batch step's 768 layer-0 tiles would each read their
     // rows' indices across the host link: its slot is copied to the device
@@ -1201,6 +1219,10 @@ int oac_sac_stage_host_idx(oac_sac* h, const int64_t* idx, int64_t bc, void* str
 
 int oac_sac_set_step_graph(oac_sac* h, void* graph_exec, int flags) {
   if (!h) { set_error("null handle"); return 1; }
+  if (h->plan.c.kind == OAC_KIND_DDPG) {
+    set_error("oac_sac_set_step_graph: DDPG (kind %d) has no data-parallel step", h->plan.c.kind);
+    return 1;
+  }
   h->plan.ext_exec = reinterpret_cast<hipGraphExec_t>(graph_exec);
   h->plan.ext_flags = (flags | OAC_STEP_GATHER) & ~OAC_STEP_USE_GRAPH;
   return 0;
@@ -1232,12 +1254,20 @@ int oac_sac_step_host_idx(oac_sac* h, const int64_t* idx, int64_t bc, int flags,
 
 int oac_sac_step_phase(oac_sac* h, int phase, int flags, void* stream) {
   if (!h) { set_error("null handle"); return 1; }
+  if (h->plan.c.kind == OAC_KIND_DDPG) {
+    set_error("oac_sac_step_phase: DDPG (kind %d) has no data-parallel step", h->plan.c.kind);
+    return 1;
+  }
   return step_phase(h->plan, phase, flags, reinterpret_cast<hipStream_t>(stream));
 }
 
 int oac_sac_set_allreduce(oac_sac* h, oac_allreduce_fn fn, void* ctx, int flags) {
   if (!h) { set_error("null handle"); return 1; }
   SacPlan& p = h->plan;
+  if (p.c.kind == OAC_KIND_DDPG) {
+    set_error("oac_sac_set_allreduce: DDPG (kind %d) has no data-parallel step", p.c.kind);
+    return 1;
+  }
   if (fn && (flags & OAC_DP_OVERLAP) && !p.side) {
     OAC_HIP_CHECK(hipStreamCreateWithFlags(&p.side, hipStreamNonBlocking));
     OAC_HIP_CHECK(hipEventCreateWithFlags(&p.ev_fork, hipEventDisableTiming));
@@ -1266,6 +1296,7 @@ int oac_sac_workspace_view(oac_sac* h, int which, int64_t* offset, int64_t* rows
   if (which == OAC_WS_H1P || which == OAC_WS_H2P)
     id = (h->plan.c.kind == OAC_KIND_SAC || h->plan.c.kind == OAC_KIND_PARTICLE)
              ? (which == OAC_WS_H1P ? W_H1P : W_H2P) : which;
+  if (h->plan.c.kind == OAC_KIND_DDPG) id = ddpg_ws_alias(which);
   const WsBuf& w = h->plan.ws[id];
   *offset = w.off; *rows = w.rows; *cols = w.cols;
   if (which == OAC_WS_BATCH || which == OAC_WS_EPS1 || which == OAC_WS_EPS2)

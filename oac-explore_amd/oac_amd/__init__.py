@@ -5,6 +5,7 @@ Drop-in replacements for the reference's hot-path interfaces:
   ParticleTrainer                    trainer/particle_trainer.py (p-oac recipes, share_layers)
   ParticleTrainerOAC                 trainer/particle_trainer_oac.py (share_layers)
   GaussianTrainer                    trainer/gaussian_trainer.py (g-oac, share_layers)
+  DDPGTrainer                        trainer/ddpg_trainer.py (--alg ddpg)
   get_optimistic_exploration_action  optimistic_exploration.py
   ReplayBuffer, ReplayBufferCount    replay_buffer.py
   vec_rollout                        path_collector.py rollout over N envs, one call per step
@@ -15,6 +16,7 @@ from .trainer import SACTrainer, row_layout  # noqa: F401
 from .particle_trainer import ParticleTrainer  # noqa: F401
 from .particle_trainer_oac import ParticleTrainer as ParticleTrainerOAC  # noqa: F401
 from .gaussian_trainer import GaussianTrainer  # noqa: F401
+from .ddpg_trainer import DDPGTrainer  # noqa: F401
 from .replay_buffer import ReplayBuffer, ReplayBufferCount, DeviceBatch, DeviceIndexStream  # noqa: F401
 from .optimistic_exploration import (get_optimistic_exploration_action,  # noqa: F401
                                      get_optimistic_exploration_actions)

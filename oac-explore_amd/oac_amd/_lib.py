@@ -17,6 +17,7 @@ OAC_KIND_SAC = 0
 OAC_KIND_PARTICLE = 1
 OAC_KIND_GAUSS = 2
 OAC_KIND_PARTICLE_UB = 3
+OAC_KIND_DDPG = 4
 
 OAC_STEP_GATHER = 1
 OAC_STEP_DEVICE_EPS = 2
@@ -154,6 +155,10 @@ _SIGS = {
                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                        ctypes.c_void_p, ctypes.c_void_p]),
+    "oac_policy_eval_fixed_std": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+                                                 ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
+                                                 ctypes.c_int64, ctypes.c_int] +
+                                  [ctypes.c_void_p] * 9),
     "oac_mt_seed_host": (ctypes.c_int, [ctypes.c_uint32, ctypes.c_void_p]),
     "oac_replay_sample_indices": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int,
                                                  ctypes.c_void_p, ctypes.c_void_p]),

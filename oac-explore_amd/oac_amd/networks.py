@@ -141,9 +141,15 @@ class ArenaFlattenMlp(nn.Module):
 
 class ArenaTanhGaussianPolicy(nn.Module):
     """TanhGaussianPolicy (trainer/policies.py:195-316) over the arena; the
-    two heads are stored stacked so the kernels read them as one matrix."""
+    two heads are stored stacked so the kernels read them as one matrix.
 
-    def __init__(self, arena, base, layout, obs_dim, act_dim, hidden):
+    ``std`` (a scalar or [act_dim] array): the fixed-std policy main.py builds
+    for ``--alg ddpg`` (policies.py:244-249; main.py:144-149, 562-563).  It has
+    no ``last_fc_log_std`` module -- ``state_dict`` holds the six reference
+    keys; the arena's log-std rows stay unused -- and ``forward`` returns
+    ``std`` / ``log_std = log(std)`` as the reference does (policies.py:280-282)."""
+
+    def __init__(self, arena, base, layout, obs_dim, act_dim, hidden, std=None):
         super().__init__()
         L = layout
         Da = act_dim
@@ -154,11 +160,19 @@ class ArenaTanhGaussianPolicy(nn.Module):
         self.fc1 = _ArenaLinear(_view(arena, base + L.pol_fc1_w, hidden, hidden),
                                 _view(arena, base + L.pol_fc1_b, hidden))
         self.last_fc = _ArenaLinear(hw[:Da], hb[:Da])
-        self.last_fc_log_std = _ArenaLinear(hw[Da:], hb[Da:])
+        if std is None:
+            self.last_fc_log_std = _ArenaLinear(hw[Da:], hb[Da:])
         self.fcs = [self.fc0, self.fc1]
         self.obs_dim, self.action_dim = obs_dim, act_dim
         self.input_size, self.output_size = obs_dim, act_dim
-        self.std = None
+        self.std = self.log_std = None
+        if std is not None:
+            std64 = np.broadcast_to(np.asarray(std, np.float64), (Da,)).copy()
+            log_std = np.log(std64)
+            assert ((LOG_SIG_MIN <= log_std) & (log_std <= LOG_SIG_MAX)).all()   # policies.py:246-247
+            dev = arena.device
+            self.std = torch.as_tensor(std64, dtype=torch.float32, device=dev)
+            self.log_std = torch.as_tensor(log_std, dtype=torch.float32, device=dev)
         self.arena, self.base = arena, base
         self.hidden = hidden
         self._offs = _offsets(L.pol_fc0_w, L.pol_fc0_b, L.pol_fc1_w, L.pol_fc1_b, L.pol_head_w,
@@ -183,16 +197,27 @@ class ArenaTanhGaussianPolicy(nn.Module):
         sample = not deterministic
         eps = torch.randn(N, Da, device=dev) if sample else None
         lp = e(N) if (sample and return_log_prob) else None
-        _lib.check(_lib.lib().oac_policy_eval(
-            ctypes.c_void_p(self.arena.data_ptr() + 4 * self.base), self._offs, self.obs_dim, Da,
-            self.hidden, _lib.ptr(x), self.obs_dim, N, _lib.ptr(eps), _lib.ptr(action),
-            _lib.ptr(mean), _lib.ptr(log_std), _lib.ptr(lp), _lib.ptr(std), _lib.ptr(pre),
-            _lib.stream_ptr(torch.cuda.current_stream(dev))))
+        net = ctypes.c_void_p(self.arena.data_ptr() + 4 * self.base)
+        if self.std is not None:   # fixed std: oac_policy_eval_fixed_std, no log-std head read
+            _lib.check(_lib.lib().oac_policy_eval_fixed_std(
+                net, self._offs, self.obs_dim, Da, self.hidden, _lib.ptr(x), self.obs_dim, N,
+                _lib.ptr(self.std), _lib.ptr(eps), _lib.ptr(action), _lib.ptr(mean),
+                _lib.ptr(log_std), _lib.ptr(lp), _lib.ptr(std), _lib.ptr(pre),
+                _lib.stream_ptr(torch.cuda.current_stream(dev))))
+        else:
+            _lib.check(_lib.lib().oac_policy_eval(
+                net, self._offs, self.obs_dim, Da, self.hidden, _lib.ptr(x), self.obs_dim, N,
+                _lib.ptr(eps), _lib.ptr(action), _lib.ptr(mean), _lib.ptr(log_std), _lib.ptr(lp),
+                _lib.ptr(std), _lib.ptr(pre), _lib.stream_ptr(torch.cuda.current_stream(dev))))
         if lp is not None:
             log_prob = lp.view(N, 1)
         else:
             log_prob = torch.zeros_like(action)
             pre = mean
+        if self.std is not None:   # the reference returns its [act_dim] tensors (policies.py:281-282)
+            rows = (action, mean, log_prob, pre)
+            action, mean, log_prob, pre = (t[0] for t in rows) if one else rows
+            return action, mean, self.log_std, log_prob, self.std, pre
         out = (action, mean, log_std, log_prob, std, pre)
         return tuple(t[0] for t in out) if one else out
 

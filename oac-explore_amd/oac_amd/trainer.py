@@ -43,7 +43,7 @@ def row_layout(obs_dim, act_dim):
                 off_term=off_term, off_next_obs=off_next)
 
 
-def _dims_from_state(pol_sd, q_sd):
+def _dims_from_state(pol_sd, q_sd, fixed_std=False):
     for sd in (pol_sd, q_sd):
         n_hidden = sum(1 for k in sd if k.startswith("fc") and k.endswith(".weight"))
         if n_hidden != 2:
@@ -53,7 +53,7 @@ def _dims_from_state(pol_sd, q_sd):
     Da = pol_sd["last_fc.weight"].shape[0]
     if q_sd["fc0.weight"].shape != (H, Do + Da) or pol_sd["fc1.weight"].shape != (H, H):
         raise ValueError("policy / critic shapes are inconsistent")
-    if "last_fc_log_std.weight" not in pol_sd:
+    if "last_fc_log_std.weight" not in pol_sd and not fixed_std:   # (fixed std: DDPGTrainer only)
         raise ValueError("only the learned-std TanhGaussianPolicy (std=None) is supported")
     return Do, Da, H, q_sd["last_fc.weight"].shape[0]
 
