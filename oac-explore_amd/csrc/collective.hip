@@ -7,7 +7,7 @@
 // per step (trainer/trainer.py:139-210 order: the alpha sum before the TD
 // target, the critic gradients before the critic Adam, the policy gradients
 // before the policy Adam).  The library issues them itself between its own
-// launches (sac_plan.hip, run_step_dp) through an oac_allreduce_fn; this file
+// launches (plan_api.hip, run_step_dp) through an oac_allreduce_fn; this file
 // is the RCCL implementation of that hook.
 //
 // librccl is loaded at run time from the path the caller passes -- the

@@ -86,8 +86,7 @@ int ddpg_ws_alias(int which) {
 void ddpg_layout_workspace(SacPlan& p) {
   const oac_sac_config& c = p.c;
   const int64_t B = c.batch, H = c.hidden, Da = c.act_dim;
-  for (int i = 0; i < kMaxWs; ++i) p.ws[i] = {0, 0, 0};
-  auto set = [&](int id, int64_t r, int64_t cl) { p.ws[id] = {0, r, cl}; };
+  auto set = begin_layout(p);
   set(OAC_WS_BATCH, B, c.row_stride);
   for (int id : {OAC_WS_HEAD1, OAC_WS_HEAD2}) set(id, B, 2 * Da);
   for (int id : {OAC_WS_ACT1, OAC_WS_ACT2}) set(id, B, Da);
@@ -99,14 +98,7 @@ void ddpg_layout_workspace(SacPlan& p) {
   for (int id : {D_DH1Q, D_DH1N, D_DH2P, D_DH1P}) set(id, B, H);
   set(D_DHEAD, B, 2 * Da);
   if (can_fuse_adam(p)) set(D_QSHADOW, 1, p.L.q_size);   // (same indexing as the critic block)
-  if (p.S_q > 1) set(WS_GSLAB_Q, p.S_q, q_group(p));
-  if (p.S_p > 1) set(WS_GSLAB_P, p.S_p, p_group(p));
-  int64_t off = 0;
-  for (int i = 0; i < kMaxWs; ++i) {
-    p.ws[i].off = off;
-    off = al64(off + p.ws[i].rows * p.ws[i].cols);
-  }
-  p.L.workspace_floats = off + 64;   // tail pad: GEMM k-contiguous loads may read 7 floats past a row
+  finish_layout(p);
 }
 
 // everything the pre-step parameters determine, through the TD target and the
@@ -124,15 +116,7 @@ static int ddpg_forward(SacPlan& p, int flags, hipStream_t s) {
   const float* R0 = direct ? p.b.replay : X;   // rows base: the replay (indexed) or the batch
   const float* obs = R0 + c.off_obs;
   const float* nobs = R0 + c.off_next_obs;
-  if (!direct && (flags & OAC_STEP_GATHER)) {
-    GatherArgs g;
-    std::memset(&g, 0, sizeof(g));
-    g.replay = p.b.replay; g.row_stride = RS; g.idx = gather_idx(p, flags); g.ring_slots = p.b.ring_slots;
-    g.out = X; g.B = B;
-    g.seed = c.seed; g.state = p.state();
-    TIMED(p, K_GATHER, s, OAC_HIP_CHECK(launch_gather(g, s)));
-    p.launches++;
-  }
+  if (!direct && (flags & OAC_STEP_GATHER) && step_gather(p, flags, s, 0, false)) return 1;
   const float* pol = p.b.params;
   // the policy acting on next_obs: the frozen target_policy_network, or the policy
   const float* npol = p.b.next_policy ? p.b.next_policy : pol;
@@ -140,32 +124,23 @@ static int ddpg_forward(SacPlan& p, int flags, hipStream_t s) {
   const float* tq = p.b.targets;
   {
     GemmBatch gb{};
-    gb.publish = p.state(); gb.pub_beta1 = c.beta1; gb.pub_beta2 = c.beta2;   // step's Adam constants
-    add(gb, t_fwd(obs, RS, B, Do, pol + L.pol_fc0_w, Do, H, p.W(D_H1P), H, EPI_BIAS_RELU, pol + L.pol_fc0_b));
-    add(gb, t_fwd(nobs, RS, B, Do, npol + L.pol_fc0_w, Do, H, p.W(D_H1P2), H, EPI_BIAS_RELU, npol + L.pol_fc0_b));
-    GemmTask t = t_fwd(obs, RS, B, Do, q + L.q_fc0_w, Dq, H, p.W(D_P), H, EPI_BIAS_RANK_RELU, q + L.q_fc0_b);
-    t.U = R0 + c.off_act; t.ldu = RS; t.V = q + L.q_fc0_w + Do; t.ldv = Dq; t.R = Da;
-    t.C2 = p.W(D_H1Q); t.ldc2 = H;
-    add(gb, t);
-    add(gb, t_fwd(nobs, RS, B, Do, tq + L.q_fc0_w, Dq, H, p.W(D_PT), H, EPI_BIAS, tq + L.q_fc0_b));
-    if (direct) {
+    publish_step(p, gb);
+    add(gb, pol_l0(p, pol, obs, D_H1P));
+    add(gb, pol_l0(p, npol, nobs, D_H1P2));
+    add(gb, critic_l0_rank(p, q, obs, R0 + c.off_act, RS, D_P, D_H1Q));
+    add(gb, target_proj(p, tq, nobs, D_PT));
+    if (direct) {   // (this step never captures: the staged indices go as kernel arguments)
       p.trace |= OAC_TRACE_DIRECT;
-      for (int i = 0; i < gb.ntasks; ++i) gb.t[i].a_rows = 1;
-      RowGather& g = gb.rg;
-      g.ring = p.host_ring; g.slots = p.b.ring_slots; g.B = B; g.state = p.state();
-      g.replay = p.b.replay; g.row_stride = RS; g.out = X;
-      if (p.inline_ok && B <= kInlineRows) g.inl = p.inline_rows;   // the staged indices as kernel arguments
-      g.seed = c.seed;
-      g.blocks = std::max(1, (B + 7) / 8);   // a wave per row (>= 8 waves per workgroup)
+      direct_rows(p, gb, p.host_ring, X, p.inline_ok && B <= kInlineRows);
     }
     if (run_gemm(p, gb, s)) return 1;
     p.inline_ok = false;   // (one staging call, one step)
   }
   {
     GemmBatch gb{};
-    add(gb, t_fwd(p.W(D_H1P), H, B, H, pol + L.pol_fc1_w, H, H, p.W(D_H2P), H, EPI_BIAS_RELU, pol + L.pol_fc1_b));
-    add(gb, t_fwd(p.W(D_H1P2), H, B, H, npol + L.pol_fc1_w, H, H, p.W(D_H2P2), H, EPI_BIAS_RELU, npol + L.pol_fc1_b));
-    add(gb, t_fwd(p.W(D_H1Q), H, B, H, q + L.q_fc1_w, H, H, p.W(D_H2Q), H, EPI_BIAS_RELU, q + L.q_fc1_b));
+    add(gb, pol_l1(p, pol, D_H1P, D_H2P));
+    add(gb, pol_l1(p, npol, D_H1P2, D_H2P2));
+    add(gb, critic_l1(p, q, D_H1Q, D_H2Q));
     if (run_gemm(p, gb, s)) return 1;
   }
   {  // both heads, a = tanh(mean), and layer 0 of the critics fed with them
@@ -182,13 +157,12 @@ static int ddpg_forward(SacPlan& p, int flags, hipStream_t s) {
     s1.h2 = p.W(D_H2P2); s1.wh = npol + L.pol_head_w; s1.bh = npol + L.pol_head_b;
     s1.head = p.W(OAC_WS_HEAD2); s1.act = p.W(OAC_WS_ACT2);
     s1.n_nets = 1; s1.wa[0] = tq + L.q_fc0_w + Do; s1.pre[0] = p.W(D_PT); s1.h1[0] = p.W(D_H1T);
-    TIMED(p, K_ROW, s, OAC_HIP_CHECK(launch_policy_head(a, 2, s)));
-    p.launches++;
+    RUN_ROW(p, s, launch_policy_head(a, 2, s));
   }
   {
     GemmBatch gb{};
-    add(gb, t_fwd(p.W(D_H1N), H, B, H, q + L.q_fc1_w, H, H, p.W(D_H2N), H, EPI_BIAS_RELU, q + L.q_fc1_b));
-    add(gb, t_fwd(p.W(D_H1T), H, B, H, tq + L.q_fc1_w, H, H, p.W(D_H2T), H, EPI_BIAS_RELU, tq + L.q_fc1_b));
+    add(gb, critic_l1(p, q, D_H1N, D_H2N));
+    add(gb, critic_l1(p, tq, D_H1T, D_H2T));
     if (run_gemm(p, gb, s)) return 1;
   }
   {
@@ -201,8 +175,7 @@ static int ddpg_forward(SacPlan& p, int flags, hipStream_t s) {
     a.reward_scale = c.reward_scale; a.discount = c.discount; a.B = B;
     a.y = p.W(OAC_WS_Y); a.dq = p.W(D_DQ); a.gq = p.W(D_GQ); a.sqe = p.W(OAC_WS_SQE1);
     a.qnew = p.W(OAC_WS_QNEW);
-    TIMED(p, K_ROW, s, OAC_HIP_CHECK(launch_ddpg_targets(a, s)));
-    p.launches++;
+    RUN_ROW(p, s, launch_ddpg_targets(a, s));
   }
   return 0;
 }
@@ -210,10 +183,7 @@ static int ddpg_forward(SacPlan& p, int flags, hipStream_t s) {
 // -mean(q_new) back to layer 1 of Q(obs, a~): post-step layer 1 and last layer
 // at qw (the critic's block in the parameters, or the shadow), pre-step masks
 static void add_qnew_bwd(SacPlan& p, GemmBatch& gb, const float* qw) {
-  const int B = p.c.batch, H = p.c.hidden;
-  GemmTask d = t_dx(nullptr, 0, B, H, qw + p.L.q_fc1_w, H, H, p.W(D_DH1N), H, p.W(D_H1N), H);
-  set_rank1(d, p.W(D_GQ), qw + p.L.q_last_w, p.W(D_H2N), H);
-  add(gb, d);
+  add(gb, critic_rank1_dx(p, qw, D_GQ, D_H2N, D_DH1N, D_H1N));
 }
 
 // critic gradients (into grad_q); fused: its Adam + Polyak complete in the
@@ -221,9 +191,7 @@ static void add_qnew_bwd(SacPlan& p, GemmBatch& gb, const float* qw) {
 static int ddpg_critic_backward(SacPlan& p, hipStream_t s, bool fused) {
   const oac_sac_config& c = p.c;
   const oac_sac_layout& L = p.L;
-  const int B = c.batch, H = c.hidden, Do = c.obs_dim, Da = c.act_dim, RS = c.row_stride;
-  const int Dq = Do + Da;
-  float* X = p.W(OAC_WS_BATCH);
+  const int B = c.batch, H = c.hidden;
   const float* q = p.b.params + L.q1_base;
   float* gq = grad_q(p);
   const long gs = q_group(p);
@@ -231,18 +199,10 @@ static int ddpg_critic_backward(SacPlan& p, hipStream_t s, bool fused) {
      // tasks' rank-1 A operand, never stored (as the SAC step's phase 1)
     GemmBatch gb{};
     const bool fold = p.cfg == 0 && p.sp_q1.S == 1 && p.sp_ql.S == 1;
-    GemmTask t = t_dw(nullptr, 0, H, B, p.W(D_H1Q), H, H, gq + L.q_fc1_w, gq + L.q_fc1_b, gs, p.sp_q1);
-    set_rank1(t, p.W(D_DQ), q + L.q_last_w, p.W(D_H2Q), H);
-    if (fold) {   // the layer-1 bias column and the last layer's dW / db in the first column block's tiles
-      t.N = H; t.b_ones = 0; t.fold = 1;
-      t.C2 = gq + L.q_last_w; t.ldc2 = (long)L.q_last_b - (long)L.q_last_w;
-    }
-    add(gb, t);
+    add(gb, critic_rank1_dw(p, q, gq, D_DQ, D_H2Q, D_H1Q, fold));
     if (!fold)
       add(gb, t_dw(p.W(D_DQ), 1, 1, B, p.W(D_H2Q), H, H, gq + L.q_last_w, gq + L.q_last_b, gs, p.sp_ql));
-    GemmTask d = t_dx(nullptr, 0, B, H, q + L.q_fc1_w, H, H, p.W(D_DH1Q), H, p.W(D_H1Q), H);
-    set_rank1(d, p.W(D_DQ), q + L.q_last_w, p.W(D_H2Q), H);
-    add(gb, d);
+    add(gb, critic_rank1_dx(p, q, D_DQ, D_H2Q, D_DH1Q, D_H1Q));
     if (fused && shadow_on(p)) {   // layer 1 + last layer: Adam in the dW epilogues, into the shadow
       AdamArgs a = critic_adam(p, 0, nullptr);
       a.no_book = 1;   // (the layer-0 launch does the step's bookkeeping)
@@ -253,7 +213,7 @@ static int ddpg_critic_backward(SacPlan& p, hipStream_t s, bool fused) {
   }
   {
     GemmBatch gb{};
-    add(gb, t_dw(p.W(D_DH1Q), H, H, B, X + c.off_obs, RS, Dq, gq + L.q_fc0_w, gq + L.q_fc0_b, gs, p.sp_q0));
+    add(gb, critic_l0_dw(p, D_DH1Q));
     if (fused) {   // critic Adam + Polyak in the epilogue
       const long off[1] = {(long)L.q_fc1_w};
       const long n[1] = {(long)(L.q_size - L.q_fc1_w)};
@@ -275,9 +235,8 @@ static int ddpg_critic_backward(SacPlan& p, hipStream_t s, bool fused) {
 static int ddpg_policy_backward(SacPlan& p, hipStream_t s, bool fused) {
   const oac_sac_config& c = p.c;
   const oac_sac_layout& L = p.L;
-  const int B = c.batch, H = c.hidden, Do = c.obs_dim, Da = c.act_dim, RS = c.row_stride;
+  const int B = c.batch, H = c.hidden, Do = c.obs_dim, Da = c.act_dim;
   const int Dq = Do + Da;
-  float* X = p.W(OAC_WS_BATCH);
   const float* pol = p.b.params;
   const float* q = p.b.params + L.q1_base;
   const bool merged = fused && shadow_on(p);   // (then the critic layer-0 dW launch ran it)
@@ -296,27 +255,23 @@ static int ddpg_policy_backward(SacPlan& p, hipStream_t s, bool fused) {
     a.act = p.W(OAC_WS_ACT1); a.dhead = p.W(D_DHEAD);
     if (hd2) { a.wh = pol + L.pol_head_w; a.h2 = p.W(D_H2P); a.dh2 = p.W(D_DH2P); }
     a.B = B; a.H = H; a.Da = Da;
-    TIMED(p, K_ROW, s, OAC_HIP_CHECK(launch_ddpg_head_backward(a, s)));
-    p.launches++;
+    RUN_ROW(p, s, launch_ddpg_head_backward(a, s));
   }
-  const long pg = p_group(p);
-  float* gp = grad_p(p);
   {
     GemmBatch gb{};
-    add(gb, t_dw(p.W(D_DHEAD), 2 * Da, 2 * Da, B, p.W(D_H2P), H, H, gp + L.pol_head_w,
-                 gp + L.pol_head_b, pg, p.sp_ph));
+    add(gb, pol_head_dw(p, 0, D_DHEAD, D_H2P));
     if (!hd2) {
-      add(gb, t_dx(p.W(D_DHEAD), 2 * Da, B, 2 * Da, pol + L.pol_head_w, H, H, p.W(D_DH2P), H, p.W(D_H2P), H));
+      add(gb, pol_head_dx(p, 0, D_DHEAD, D_DH2P, D_H2P));
       if (run_gemm(p, gb, s)) return 1;
       gb = GemmBatch{};
     }
-    add(gb, t_dw(p.W(D_DH2P), H, H, B, p.W(D_H1P), H, H, gp + L.pol_fc1_w, gp + L.pol_fc1_b, pg, p.sp_p1));
-    add(gb, t_dx(p.W(D_DH2P), H, B, H, pol + L.pol_fc1_w, H, H, p.W(D_DH1P), H, p.W(D_H1P), H));
+    add(gb, pol_l1_dw(p, 0, D_DH2P, D_H1P));
+    add(gb, pol_l1_dx(p, 0, D_DH2P, D_DH1P, D_H1P));
     if (run_gemm(p, gb, s)) return 1;
   }
   {
     GemmBatch gb{};
-    add(gb, t_dw(p.W(D_DH1P), H, H, B, X + c.off_obs, RS, Do, gp + L.pol_fc0_w, gp + L.pol_fc0_b, pg, p.sp_p0));
+    add(gb, pol_l0_dw(p, 0, D_DH1P));
     if (fused) {   // policy Adam in the epilogue; advances the step
       const long off[1] = {(long)L.pol_fc1_w};
       const long n[1] = {(long)(L.pol_size - L.pol_fc1_w)};
@@ -327,23 +282,15 @@ static int ddpg_policy_backward(SacPlan& p, hipStream_t s, bool fused) {
   return 0;
 }
 
-int ddpg_run_step(SacPlan& p, int flags, hipStream_t s) {
+int ddpg_run_step(SacPlan& p, int flags, hipStream_t s, int, int) {
   p.launches = 0;
   const bool fused = can_fuse_adam(p);
   if (fused) p.trace |= OAC_TRACE_FUSED;
   if (ddpg_forward(p, flags, s)) return 1;
   if (ddpg_critic_backward(p, s, fused)) return 1;
-  if (!fused) {
-    AdamArgs a = critic_adam(p, 0, nullptr);
-    TIMED(p, K_ADAM, s, OAC_HIP_CHECK(launch_adam(a, s)));
-    p.launches++;
-  }
+  if (!fused && run_adam(p, critic_adam(p, 0, nullptr), s)) return 1;
   if (ddpg_policy_backward(p, s, fused)) return 1;
-  if (!fused) {
-    AdamArgs a = policy_adam(p, 0, nullptr);
-    TIMED(p, K_ADAM, s, OAC_HIP_CHECK(launch_adam(a, s)));
-    p.launches++;
-  }
+  if (!fused && run_adam(p, policy_adam(p, 0, nullptr), s)) return 1;
   return 0;
 }
 

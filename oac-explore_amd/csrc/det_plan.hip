@@ -57,8 +57,7 @@ static_assert(G_COUNT <= WS_GSLAB_Q, "workspace ids");
 void det_layout_workspace(SacPlan& p) {
   const oac_sac_config& c = p.c;
   const int64_t B = c.batch, H = c.hidden, Da = c.act_dim, K = c.q_out;
-  for (int i = 0; i < kMaxWs; ++i) p.ws[i] = {0, 0, 0};
-  auto set = [&](int id, int64_t r, int64_t cl) { p.ws[id] = {0, r, cl}; };
+  auto set = begin_layout(p);
   set(OAC_WS_BATCH, B, c.row_stride);
   for (int id : {OAC_WS_HEAD1, OAC_WS_HEAD2, OAC_WS_HEAD3}) set(id, B, 2 * Da);
   for (int id : {OAC_WS_ACT1, OAC_WS_ACT2, OAC_WS_ACT3}) set(id, B, Da);
@@ -73,14 +72,7 @@ void det_layout_workspace(SacPlan& p) {
     set(id, B, H);
   for (int id : {G_DA, G_DA3}) set(id, B, Da);
   for (int id : {G_DHEAD, G_DHEAD3}) set(id, B, 2 * Da);
-  if (p.S_q > 1) set(WS_GSLAB_Q, p.S_q, q_group(p));
-  if (p.S_p > 1) set(WS_GSLAB_P, p.S_p, p_group(p));
-  int64_t off = 0;
-  for (int i = 0; i < kMaxWs; ++i) {
-    p.ws[i].off = off;
-    off = al64(off + p.ws[i].rows * p.ws[i].cols);
-  }
-  p.L.workspace_floats = off + 64;   // tail pad: GEMM k-contiguous loads may read 7 floats past a row
+  finish_layout(p);
 }
 
 // ------------------------------------------------------------------ phases
@@ -93,23 +85,9 @@ static int dphase0(SacPlan& p, int flags, hipStream_t s) {
   float* X = p.W(OAC_WS_BATCH);
   const float* obs = X + c.off_obs;
   const float* nobs = X + c.off_next_obs;
-  if (flags & OAC_STEP_GATHER) {
-    GatherArgs g;
-    std::memset(&g, 0, sizeof(g));
-    g.replay = p.b.replay; g.row_stride = RS; g.idx = gather_idx(p, flags); g.ring_slots = p.b.ring_slots;
-    g.out = X; g.B = B;
-    g.seed = c.seed; g.state = p.state();
-    TIMED(p, K_GATHER, s, OAC_HIP_CHECK(launch_gather(g, s)));
-    p.launches++;
-  }
-  if ((flags & (OAC_STEP_GATHER | OAC_STEP_COUNTS)) == (OAC_STEP_GATHER | OAC_STEP_COUNTS) &&
-      p.b.counts) {   // ring path of a counts=True trainer: this draw's counts on the device
-    CountsStepArgs ca{p.b.counts, p.b.count_tags, p.b.count_epoch, gather_idx(p, flags), p.b.ring_slots,
-                      p.state(), c.batch, p.W(OAC_WS_COUNTS)};
-    TIMED(p, K_GATHER, s, OAC_HIP_CHECK(launch_counts_step(ca, s)));
-    p.launches++;
-  }
-    const float* pol = p.b.params;
+  if ((flags & OAC_STEP_GATHER) && step_gather(p, flags, s, 0, false)) return 1;   // (no eps: deterministic)
+  if (step_counts(p, flags, s)) return 1;
+  const float* pol = p.b.params;
   const float* tpol = p.b.params + L.tpol_base;
   // the policy acting on next_obs: target_policy (mean_update), the
   // use_target_policy network, or the policy itself
@@ -118,23 +96,20 @@ static int dphase0(SacPlan& p, int flags, hipStream_t s) {
   const float* tq = p.b.targets;
   {
     GemmBatch gb{};
-    add(gb, t_fwd(obs, RS, B, Do, pol + L.pol_fc0_w, Do, H, p.W(G_H1P), H, EPI_BIAS_RELU, pol + L.pol_fc0_b));
-    gb.publish = p.state(); gb.pub_beta1 = c.beta1; gb.pub_beta2 = c.beta2;   // step's Adam constants
-    add(gb, t_fwd(nobs, RS, B, Do, npol + L.pol_fc0_w, Do, H, p.W(G_H1P2), H, EPI_BIAS_RELU, npol + L.pol_fc0_b));
-    add(gb, t_fwd(obs, RS, B, Do, tpol + L.pol_fc0_w, Do, H, p.W(G_H1TP), H, EPI_BIAS_RELU, tpol + L.pol_fc0_b));
-    GemmTask t = t_fwd(obs, RS, B, Do, q + L.q_fc0_w, Dq, H, p.W(G_P), H, EPI_BIAS_RANK_RELU, q + L.q_fc0_b);
-    t.U = X + c.off_act; t.ldu = RS; t.V = q + L.q_fc0_w + Do; t.ldv = Dq; t.R = Da;
-    t.C2 = p.W(G_H1Q); t.ldc2 = H;
-    add(gb, t);
-    add(gb, t_fwd(nobs, RS, B, Do, tq + L.q_fc0_w, Dq, H, p.W(G_PT), H, EPI_BIAS, tq + L.q_fc0_b));
+    publish_step(p, gb);
+    add(gb, pol_l0(p, pol, obs, G_H1P));
+    add(gb, pol_l0(p, npol, nobs, G_H1P2));
+    add(gb, pol_l0(p, tpol, obs, G_H1TP));
+    add(gb, critic_l0_rank(p, q, obs, X + c.off_act, RS, G_P, G_H1Q));
+    add(gb, target_proj(p, tq, nobs, G_PT));
     if (run_gemm(p, gb, s)) return 1;
   }
   {
     GemmBatch gb{};
-    add(gb, t_fwd(p.W(G_H1P), H, B, H, pol + L.pol_fc1_w, H, H, p.W(G_H2P), H, EPI_BIAS_RELU, pol + L.pol_fc1_b));
-    add(gb, t_fwd(p.W(G_H1P2), H, B, H, npol + L.pol_fc1_w, H, H, p.W(G_H2P2), H, EPI_BIAS_RELU, npol + L.pol_fc1_b));
-    add(gb, t_fwd(p.W(G_H1TP), H, B, H, tpol + L.pol_fc1_w, H, H, p.W(G_H2TP), H, EPI_BIAS_RELU, tpol + L.pol_fc1_b));
-    add(gb, t_fwd(p.W(G_H1Q), H, B, H, q + L.q_fc1_w, H, H, p.W(G_H2Q), H, EPI_BIAS_RELU, q + L.q_fc1_b));
+    add(gb, pol_l1(p, pol, G_H1P, G_H2P));
+    add(gb, pol_l1(p, npol, G_H1P2, G_H2P2));
+    add(gb, pol_l1(p, tpol, G_H1TP, G_H2TP));
+    add(gb, critic_l1(p, q, G_H1Q, G_H2Q));
     if (run_gemm(p, gb, s)) return 1;
   }
   {  // the three heads, a = tanh(mean), and the target critic's action
@@ -154,8 +129,7 @@ static int dphase0(SacPlan& p, int flags, hipStream_t s) {
     HeadSeg& s2 = a.seg[2];   // target_policy(obs) -> a~_T (phase 2)
     s2.h2 = p.W(G_H2TP); s2.wh = tpol + L.pol_head_w; s2.bh = tpol + L.pol_head_b;
     s2.head = p.W(OAC_WS_HEAD3); s2.act = p.W(OAC_WS_ACT3);
-    TIMED(p, K_ROW, s, OAC_HIP_CHECK(launch_policy_head(a, 3, s)));
-    p.launches++;
+    RUN_ROW(p, s, launch_policy_head(a, 3, s));
   }
   return 0;
 }
@@ -164,15 +138,14 @@ static int dphase0(SacPlan& p, int flags, hipStream_t s) {
 static int dphase1(SacPlan& p, int flags, hipStream_t s, bool fused) {
   const oac_sac_config& c = p.c;
   const oac_sac_layout& L = p.L;
-  const int B = c.batch, H = c.hidden, Do = c.obs_dim, Da = c.act_dim, RS = c.row_stride;
-  const int Dq = Do + Da, K = c.q_out;
+  const int B = c.batch, H = c.hidden, RS = c.row_stride, K = c.q_out;
   float* X = p.W(OAC_WS_BATCH);
   const float* q = p.b.params + L.q1_base;
   const float* tq = p.b.targets;
   {  // target critic layer 1, and the critic's outputs Q(obs, a)
     GemmBatch gb{};
-    add(gb, t_fwd(p.W(G_H1T), H, B, H, tq + L.q_fc1_w, H, H, p.W(G_H2T), H, EPI_BIAS_RELU, tq + L.q_fc1_b));
-    add(gb, t_fwd(p.W(G_H2Q), H, B, H, q + L.q_last_w, H, K, p.W(OAC_WS_Q1), K, EPI_BIAS, q + L.q_last_b));
+    add(gb, critic_l1(p, tq, G_H1T, G_H2T));
+    add(gb, critic_last(p, q, G_H2Q, OAC_WS_Q1));
     if (run_gemm(p, gb, s)) return 1;
   }
   // the target critic's K-output last layer runs inside the targets kernel
@@ -188,8 +161,7 @@ static int dphase1(SacPlan& p, int flags, hipStream_t s, bool fused) {
     a.soft_prob = c.std_soft_update ? c.std_soft_prob : -1.f;
     a.counts = counts; a.th = th;
     a.B = B; a.dq = p.W(G_DQ); a.y = p.W(OAC_WS_Y); a.sqe = p.W(OAC_WS_SQE1);
-    TIMED(p, K_ROW, s, OAC_HIP_CHECK(launch_gauss_targets(a, s)));
-    p.launches++;
+    RUN_ROW(p, s, launch_gauss_targets(a, s));
   } else {
     ParticleTargetArgs a;
     std::memset(&a, 0, sizeof(a));
@@ -200,34 +172,23 @@ static int dphase1(SacPlan& p, int flags, hipStream_t s, bool fused) {
     a.loss_scale = 1.f / (float)K;                       // qf_loss /= num_particles
     a.soft_prob = c.std_soft_update ? c.std_soft_prob : -1.f;
     a.rescale_spread = c.rescale_spread;
-    TIMED(p, K_ROW, s, OAC_HIP_CHECK(launch_particle_targets(a, s)));
-    p.launches++;
+    RUN_ROW(p, s, launch_particle_targets(a, s));
   }
   {
     GemmBatch gb{};
-    float* gq = grad_q(p);
-    GemmTask tl = t_dw(p.W(G_DQ), K, K, B, p.W(G_H2Q), H, H, gq + L.q_last_w, gq + L.q_last_b,
-                 q_group(p), p.sp_ql);
-    // train_bias=False: no ones column, the frozen bias keeps a zero gradient
-    // (Adam then leaves it, and its moments, exactly unchanged)
-    if (c.freeze_q_bias) { tl.N = H; tl.b_ones = 0; tl.bias_grad = nullptr; }
-    add(gb, tl);
-    add(gb, t_dx(p.W(G_DQ), K, B, K, q + L.q_last_w, H, H, p.W(G_DH2Q), H, p.W(G_H2Q), H));
+    add(gb, critic_last_dw(p, G_DQ, G_H2Q));
+    add(gb, critic_last_dx(p, G_DQ, G_DH2Q, G_H2Q));
     if (run_gemm(p, gb, s)) return 1;
   }
   {
     GemmBatch gb{};
-    float* gq = grad_q(p);
-    add(gb, t_dw(p.W(G_DH2Q), H, H, B, p.W(G_H1Q), H, H, gq + L.q_fc1_w, gq + L.q_fc1_b,
-                 q_group(p), p.sp_q1));
-    add(gb, t_dx(p.W(G_DH2Q), H, B, H, q + L.q_fc1_w, H, H, p.W(G_DH1Q), H, p.W(G_H1Q), H));
+    add(gb, critic_l1_dw(p, G_DH2Q, G_H1Q));
+    add(gb, critic_l1_dx(p, G_DH2Q, G_DH1Q, G_H1Q));
     if (run_gemm(p, gb, s)) return 1;
   }
   {
     GemmBatch gb{};
-    float* gq = grad_q(p);
-    add(gb, t_dw(p.W(G_DH1Q), H, H, B, X + c.off_obs, RS, Dq, gq + L.q_fc0_w, gq + L.q_fc0_b,
-                 q_group(p), p.sp_q0));
+    add(gb, critic_l0_dw(p, G_DH1Q));
     if (fused) {   // critic Adam + Polyak in the epilogue (other layers: tail blocks)
       const long off[1] = {(long)L.q_fc1_w};
       const long n[1] = {(long)(L.q_size - L.q_fc1_w)};
@@ -243,27 +204,19 @@ static int dphase1(SacPlan& p, int flags, hipStream_t s, bool fused) {
 static int dphase2(SacPlan& p, hipStream_t s, bool fused) {
   const oac_sac_config& c = p.c;
   const oac_sac_layout& L = p.L;
-  const int B = c.batch, H = c.hidden, Do = c.obs_dim, Da = c.act_dim, RS = c.row_stride;
-  const int Dq = Do + Da, K = c.q_out;
+  const int B = c.batch, H = c.hidden, Da = c.act_dim, K = c.q_out;
   float* X = p.W(OAC_WS_BATCH);
-  const float* pol = p.b.params;
-  const float* tpol = p.b.params + L.tpol_base;
   const float* q = p.b.params + L.q1_base;
   {
     GemmBatch gb{};
-    for (int k = 0; k < 2; ++k) {
-      GemmTask t = t_fwd(X + c.off_obs, RS, B, Do, q + L.q_fc0_w, Dq, H, p.W(k ? G_PN3 : G_PN), H,
-                         EPI_BIAS_RANK_RELU, q + L.q_fc0_b);
-      t.U = p.W(k ? OAC_WS_ACT3 : OAC_WS_ACT1); t.ldu = Da; t.V = q + L.q_fc0_w + Do; t.ldv = Dq;
-      t.R = Da; t.C2 = p.W(k ? G_H1N3 : G_H1N); t.ldc2 = H;
-      add(gb, t);
-    }
+    add(gb, critic_l0_rank(p, q, X + c.off_obs, p.W(OAC_WS_ACT1), Da, G_PN, G_H1N));
+    add(gb, critic_l0_rank(p, q, X + c.off_obs, p.W(OAC_WS_ACT3), Da, G_PN3, G_H1N3));
     if (run_gemm(p, gb, s)) return 1;
   }
   {
     GemmBatch gb{};
-    add(gb, t_fwd(p.W(G_H1N), H, B, H, q + L.q_fc1_w, H, H, p.W(G_H2N), H, EPI_BIAS_RELU, q + L.q_fc1_b));
-    add(gb, t_fwd(p.W(G_H1N3), H, B, H, q + L.q_fc1_w, H, H, p.W(G_H2N3), H, EPI_BIAS_RELU, q + L.q_fc1_b));
+    add(gb, critic_l1(p, q, G_H1N, G_H2N));
+    add(gb, critic_l1(p, q, G_H1N3, G_H2N3));
     if (run_gemm(p, gb, s)) return 1;
   }
   // the post-step critic's last layer on (obs, a~) runs inside the seed
@@ -276,33 +229,31 @@ static int dphase2(SacPlan& p, hipStream_t s, bool fused) {
     std::memset(&a, 0, sizeof(a));
     a.qn = p.W(OAC_WS_QN1); a.qt = p.W(OAC_WS_QN2); a.hn = hn; a.std_bound = c.std_bound; a.B = B;
     a.g = p.W(G_GQ); a.gt = p.W(G_GQ3); a.ub = p.W(OAC_WS_QNEW);
-    TIMED(p, K_ROW, s, OAC_HIP_CHECK(launch_gauss_seed(a, s)));
-    p.launches++;
+    RUN_ROW(p, s, launch_gauss_seed(a, s));
   } else {
     ParticleUbSeedArgs a;
     std::memset(&a, 0, sizeof(a));
     a.qn = p.W(OAC_WS_QN1); a.qt = p.W(OAC_WS_QN2); a.hn = hn; a.B = B; a.K = K;
     a.delta_index = c.delta_index;
     a.g = p.W(G_GQ); a.gt = p.W(G_GQ3); a.ub = p.W(OAC_WS_QNEW);
-    TIMED(p, K_ROW, s, OAC_HIP_CHECK(launch_particle_ub_seed(a, s)));
-    p.launches++;
+    RUN_ROW(p, s, launch_particle_ub_seed(a, s));
   }
   {
     GemmBatch gb{};
-    add(gb, t_dx(p.W(G_GQ), K, B, K, q + L.q_last_w, H, H, p.W(G_DH2N), H, p.W(G_H2N), H));
-    add(gb, t_dx(p.W(G_GQ3), K, B, K, q + L.q_last_w, H, H, p.W(G_DH2N3), H, p.W(G_H2N3), H));
+    add(gb, critic_last_dx(p, G_GQ, G_DH2N, G_H2N));
+    add(gb, critic_last_dx(p, G_GQ3, G_DH2N3, G_H2N3));
     if (run_gemm(p, gb, s)) return 1;
   }
   {
     GemmBatch gb{};
-    add(gb, t_dx(p.W(G_DH2N), H, B, H, q + L.q_fc1_w, H, H, p.W(G_DH1N), H, p.W(G_H1N), H));
-    add(gb, t_dx(p.W(G_DH2N3), H, B, H, q + L.q_fc1_w, H, H, p.W(G_DH1N3), H, p.W(G_H1N3), H));
+    add(gb, critic_l1_dx(p, G_DH2N, G_DH1N, G_H1N));
+    add(gb, critic_l1_dx(p, G_DH2N3, G_DH1N3, G_H1N3));
     if (run_gemm(p, gb, s)) return 1;
   }
   {
     GemmBatch gb{};
-    add(gb, t_dx(p.W(G_DH1N), H, B, H, q + L.q_fc0_w + Do, Dq, Da, p.W(G_DA), Da, nullptr, 0));
-    add(gb, t_dx(p.W(G_DH1N3), H, B, H, q + L.q_fc0_w + Do, Dq, Da, p.W(G_DA3), Da, nullptr, 0));
+    add(gb, critic_act_dx(p, q, G_DH1N, G_DA, Da));
+    add(gb, critic_act_dx(p, q, G_DH1N3, G_DA3, Da));
     if (run_gemm(p, gb, s)) return 1;
   }
   {
@@ -311,34 +262,29 @@ static int dphase2(SacPlan& p, hipStream_t s, bool fused) {
     a.da[0] = p.W(G_DA); a.act[0] = p.W(OAC_WS_ACT1); a.dhead[0] = p.W(G_DHEAD);
     a.da[1] = p.W(G_DA3); a.act[1] = p.W(OAC_WS_ACT3); a.dhead[1] = p.W(G_DHEAD3);
     a.nseg = 2; a.B = B; a.act_dim = Da;
-    TIMED(p, K_ROW, s, OAC_HIP_CHECK(launch_det_head_backward(a, s)));
-    p.launches++;
+    RUN_ROW(p, s, launch_det_head_backward(a, s));
   }
-  const long pg = p_group(p);
-  float* gp = grad_p(p);
-  float* gtp = gp + L.tpol_base;
+  const long tp = L.tpol_base;   // the target_policy block's offset in the policy group
   {
     GemmBatch gb{};
-    add(gb, t_dw(p.W(G_DHEAD), 2 * Da, 2 * Da, B, p.W(G_H2P), H, H, gp + L.pol_head_w,
-                 gp + L.pol_head_b, pg, p.sp_ph));
-    add(gb, t_dx(p.W(G_DHEAD), 2 * Da, B, 2 * Da, pol + L.pol_head_w, H, H, p.W(G_DH2P), H, p.W(G_H2P), H));
-    add(gb, t_dw(p.W(G_DHEAD3), 2 * Da, 2 * Da, B, p.W(G_H2TP), H, H, gtp + L.pol_head_w,
-                 gtp + L.pol_head_b, pg, p.sp_ph));
-    add(gb, t_dx(p.W(G_DHEAD3), 2 * Da, B, 2 * Da, tpol + L.pol_head_w, H, H, p.W(G_DH2TP), H, p.W(G_H2TP), H));
+    add(gb, pol_head_dw(p, 0, G_DHEAD, G_H2P));
+    add(gb, pol_head_dx(p, 0, G_DHEAD, G_DH2P, G_H2P));
+    add(gb, pol_head_dw(p, tp, G_DHEAD3, G_H2TP));
+    add(gb, pol_head_dx(p, tp, G_DHEAD3, G_DH2TP, G_H2TP));
     if (run_gemm(p, gb, s)) return 1;
   }
   {
     GemmBatch gb{};
-    add(gb, t_dw(p.W(G_DH2P), H, H, B, p.W(G_H1P), H, H, gp + L.pol_fc1_w, gp + L.pol_fc1_b, pg, p.sp_p1));
-    add(gb, t_dx(p.W(G_DH2P), H, B, H, pol + L.pol_fc1_w, H, H, p.W(G_DH1P), H, p.W(G_H1P), H));
-    add(gb, t_dw(p.W(G_DH2TP), H, H, B, p.W(G_H1TP), H, H, gtp + L.pol_fc1_w, gtp + L.pol_fc1_b, pg, p.sp_p1));
-    add(gb, t_dx(p.W(G_DH2TP), H, B, H, tpol + L.pol_fc1_w, H, H, p.W(G_DH1TP), H, p.W(G_H1TP), H));
+    add(gb, pol_l1_dw(p, 0, G_DH2P, G_H1P));
+    add(gb, pol_l1_dx(p, 0, G_DH2P, G_DH1P, G_H1P));
+    add(gb, pol_l1_dw(p, tp, G_DH2TP, G_H1TP));
+    add(gb, pol_l1_dx(p, tp, G_DH2TP, G_DH1TP, G_H1TP));
     if (run_gemm(p, gb, s)) return 1;
   }
   {
     GemmBatch gb{};
-    add(gb, t_dw(p.W(G_DH1P), H, H, B, X + c.off_obs, RS, Do, gp + L.pol_fc0_w, gp + L.pol_fc0_b, pg, p.sp_p0));
-    add(gb, t_dw(p.W(G_DH1TP), H, H, B, X + c.off_obs, RS, Do, gtp + L.pol_fc0_w, gtp + L.pol_fc0_b, pg, p.sp_p0));
+    add(gb, pol_l0_dw(p, 0, G_DH1P));
+    add(gb, pol_l0_dw(p, tp, G_DH1TP));
     if (fused) {   // [policy | target_policy] Adam in the epilogue; advances the step
       const long off[2] = {(long)L.pol_fc1_w, (long)(L.tpol_base + L.pol_fc1_w)};
       const long n[2] = {(long)(L.pol_size - L.pol_fc1_w), (long)(L.pol_size - L.pol_fc1_w)};
@@ -349,56 +295,23 @@ static int dphase2(SacPlan& p, hipStream_t s, bool fused) {
   return 0;
 }
 
-int det_run_step(SacPlan& p, int flags, hipStream_t s) {
+int det_run_step(SacPlan& p, int flags, hipStream_t s, int, int) {
   p.launches = 0;
   const bool fused = can_fuse_adam(p);
   if (dphase0(p, flags, s)) return 1;
   if (dphase1(p, flags, s, fused)) return 1;
-  if (!fused) {
-    AdamArgs a = critic_adam(p, 0, nullptr);
-    TIMED(p, K_ADAM, s, OAC_HIP_CHECK(launch_adam(a, s)));
-    p.launches++;
-  }
+  if (!fused && run_adam(p, critic_adam(p, 0, nullptr), s)) return 1;
   if (dphase2(p, s, fused)) return 1;
-  if (!fused) {
-    AdamArgs a = policy_adam(p, 0, nullptr);
-    TIMED(p, K_ADAM, s, OAC_HIP_CHECK(launch_adam(a, s)));
-    p.launches++;
-  }
+  if (!fused && run_adam(p, policy_adam(p, 0, nullptr), s)) return 1;
   return 0;
 }
 
 // data-parallel split (no whole-batch quantity besides the gradients: the
-// phase-0 exchange is empty)
+// phase-0 exchange is empty; no alpha to commit)
 int det_step_phase(SacPlan& p, int phase, int flags, hipStream_t s) {
-  switch (phase) {
-    case 0: return dphase0(p, flags, s);
-    case 1:
-      if (dphase1(p, flags, s, false)) return 1;
-      if (p.S_q > 1) {
-        AdamArgs a = critic_adam(p, 1, nullptr);
-        OAC_HIP_CHECK(launch_adam(a, s));
-      }
-      return 0;
-    case 2: {
-      AdamArgs a = critic_adam(p, -1, nullptr);
-      OAC_HIP_CHECK(launch_adam(a, s));
-      if (dphase2(p, s, false)) return 1;
-      if (p.S_p > 1) {
-        AdamArgs b = policy_adam(p, 1, nullptr);
-        OAC_HIP_CHECK(launch_adam(b, s));
-      }
-      return 0;
-    }
-    case 3: {
-      AdamArgs a = policy_adam(p, -1, nullptr);
-      OAC_HIP_CHECK(launch_adam(a, s));
-      return 0;
-    }
-    default:
-      set_error("bad phase %d", phase);
-      return 1;
-  }
+  return dp_step_phase(
+      p, phase, s, [&] { return dphase0(p, flags, s); }, [&] { return dphase1(p, flags, s, false); },
+      [&] { return dphase2(p, s, false); }, nullptr);
 }
 
 }  // namespace oac

@@ -36,11 +36,15 @@ enum PWs {
 };
 static_assert(X_COUNT <= kMaxWs, "workspace ids");
 
+// the policy's hidden layers on obs: the first two internal buffers
+int particle_ws_alias(int which) {
+  return which == OAC_WS_H1P ? X_H1P : which == OAC_WS_H2P ? X_H2P : which;
+}
+
 void particle_layout_workspace(SacPlan& p) {
   const oac_sac_config& c = p.c;
   const int64_t B = c.batch, H = c.hidden, Da = c.act_dim, K = c.q_out;
-  for (int i = 0; i < kMaxWs; ++i) p.ws[i] = {0, 0, 0};
-  auto set = [&](int id, int64_t r, int64_t cl) { p.ws[id] = {0, r, cl}; };
+  auto set = begin_layout(p);
   set(OAC_WS_BATCH, B, c.row_stride);
   set(OAC_WS_EPS1, B, Da); set(OAC_WS_EPS2, B, Da);
   set(OAC_WS_HEAD1, B, 2 * Da); set(OAC_WS_HEAD2, B, 2 * Da);
@@ -55,14 +59,7 @@ void particle_layout_workspace(SacPlan& p) {
   set(X_DQ, B, K); set(X_GQ, B, K);
   for (int id : {X_DH2Q, X_DH1Q, X_PN, X_H1N, X_H2N, X_DH2N, X_DH1N, X_DH2P, X_DH1P}) set(id, B, H);
   set(X_DHEAD, B, 2 * Da);
-  if (p.S_q > 1) set(WS_GSLAB_Q, p.S_q, p.L.n_critics * p.L.q_size);
-  if (p.S_p > 1) set(WS_GSLAB_P, p.S_p, p.L.pol_size);
-  int64_t off = 0;
-  for (int i = 0; i < kMaxWs; ++i) {
-    p.ws[i].off = off;
-    off = al64(off + p.ws[i].rows * p.ws[i].cols);
-  }
-  p.L.workspace_floats = off + 64;   // tail pad: GEMM k-contiguous loads may read 7 floats past a row
+  finish_layout(p);
 }
 
 // ------------------------------------------------------------------ phases
@@ -90,54 +87,31 @@ static int pphase0(SacPlan& p, int flags, hipStream_t s) {
   const float* R0 = direct_big ? p.b.replay : X;
   const float* obs = R0 + c.off_obs;
   const float* nobs = R0 + c.off_next_obs;
-  if (!direct_big && (flags & (OAC_STEP_GATHER | OAC_STEP_DEVICE_EPS))) {
-    GatherArgs g;
-    std::memset(&g, 0, sizeof(g));
-    g.replay = p.b.replay; g.row_stride = RS; g.idx = gather_idx(p, flags); g.ring_slots = p.b.ring_slots;
-    g.out = X; g.B = (flags & OAC_STEP_GATHER) ? B : 0;
-    if (flags & OAC_STEP_DEVICE_EPS) {
-      g.eps1 = p.W(OAC_WS_EPS1); g.eps2 = p.W(OAC_WS_EPS2); g.n_eps = B * Da;
-    }
-    g.seed = c.seed; g.state = p.state();
-    TIMED(p, K_GATHER, s, OAC_HIP_CHECK(launch_gather(g, s)));
-    p.launches++;
-  }
-  if ((flags & (OAC_STEP_GATHER | OAC_STEP_COUNTS)) == (OAC_STEP_GATHER | OAC_STEP_COUNTS) &&
-      p.b.counts) {   // ring path of a counts=True trainer: this draw's counts on the device
-    CountsStepArgs ca{p.b.counts, p.b.count_tags, p.b.count_epoch, gather_idx(p, flags), p.b.ring_slots,
-                      p.state(), c.batch, p.W(OAC_WS_COUNTS)};
-    TIMED(p, K_GATHER, s, OAC_HIP_CHECK(launch_counts_step(ca, s)));
-    p.launches++;
-  }
+  if (!direct_big && (flags & (OAC_STEP_GATHER | OAC_STEP_DEVICE_EPS)))
+    if (step_gather(p, flags, s, 0, true)) return 1;
+  if (step_counts(p, flags, s)) return 1;
   const float* pol = p.b.params;
   const float* q = p.b.params + L.q1_base;
   const float* tq = p.b.targets;
   {
     GemmBatch gb{};
-    add(gb, t_fwd(obs, RS, B, Do, pol + L.pol_fc0_w, Do, H, p.W(X_H1P), H, EPI_BIAS_RELU, pol + L.pol_fc0_b));
-    gb.publish = p.state(); gb.pub_beta1 = c.beta1; gb.pub_beta2 = c.beta2;   // step's Adam constants
-    add(gb, t_fwd(nobs, RS, B, Do, pol + L.pol_fc0_w, Do, H, p.W(X_H1P2), H, EPI_BIAS_RELU, pol + L.pol_fc0_b));
-    GemmTask t = t_fwd(obs, RS, B, Do, q + L.q_fc0_w, Dq, H, p.W(X_P), H, EPI_BIAS_RANK_RELU, q + L.q_fc0_b);
-    t.U = R0 + c.off_act; t.ldu = RS; t.V = q + L.q_fc0_w + Do; t.ldv = Dq; t.R = Da;
-    t.C2 = p.W(X_H1Q); t.ldc2 = H;
-    add(gb, t);
-    add(gb, t_fwd(nobs, RS, B, Do, tq + L.q_fc0_w, Dq, H, p.W(X_PT), H, EPI_BIAS, tq + L.q_fc0_b));
+    publish_step(p, gb);
+    add(gb, pol_l0(p, pol, obs, X_H1P));
+    add(gb, pol_l0(p, pol, nobs, X_H1P2));
+    add(gb, critic_l0_rank(p, q, obs, R0 + c.off_act, RS, X_P, X_H1Q));
+    add(gb, target_proj(p, tq, nobs, X_PT));
     if (direct_big) {
-      for (int i = 0; i < gb.ntasks; ++i) gb.t[i].a_rows = 1;
-      RowGather& g = gb.rg;
-      g.ring = p.direct_ring; g.slots = p.b.ring_slots; g.B = B; g.state = p.state();
-      if (flags & OAC_STEP_DEVICE_EPS) {   // 512 tiles of 128 x 64: a free slot per CU
-        g.eps1 = p.W(OAC_WS_EPS1); g.eps2 = p.W(OAC_WS_EPS2); g.n_eps = B * Da; g.seed = c.seed;
-        g.blocks = 256;
-      }
+      rows_through_ring(p, gb, p.direct_ring);
+      if (flags & OAC_STEP_DEVICE_EPS)   // 512 tiles of 128 x 64: a free slot per CU
+        side_eps(p, gb, p.W(OAC_WS_EPS1), p.W(OAC_WS_EPS2), 256);
     }
     if (run_gemm(p, gb, s)) return 1;
   }
   {
     GemmBatch gb{};
-    add(gb, t_fwd(p.W(X_H1P), H, B, H, pol + L.pol_fc1_w, H, H, p.W(X_H2P), H, EPI_BIAS_RELU, pol + L.pol_fc1_b));
-    add(gb, t_fwd(p.W(X_H1P2), H, B, H, pol + L.pol_fc1_w, H, H, p.W(X_H2P2), H, EPI_BIAS_RELU, pol + L.pol_fc1_b));
-    add(gb, t_fwd(p.W(X_H1Q), H, B, H, q + L.q_fc1_w, H, H, p.W(X_H2Q), H, EPI_BIAS_RELU, q + L.q_fc1_b));
+    add(gb, pol_l1(p, pol, X_H1P, X_H2P));
+    add(gb, pol_l1(p, pol, X_H1P2, X_H2P2));
+    add(gb, critic_l1(p, q, X_H1Q, X_H2Q));
     if (run_gemm(p, gb, s)) return 1;
   }
   {  // policy heads, tanh-Gaussian sample + log-prob (both batches), and the
@@ -160,8 +134,7 @@ static int pphase0(SacPlan& p, int flags, hipStream_t s) {
     if (c.world_size > 1 && c.auto_alpha) {   // the local alpha partials for the all-reduce
       a.logp_part = p.W(OAC_WS_LOGP_PART); a.target_entropy = c.target_entropy;
     }
-    TIMED(p, K_ROW, s, OAC_HIP_CHECK(launch_policy_head(a, 2, s)));
-    p.launches++;
+    RUN_ROW(p, s, launch_policy_head(a, 2, s));
   }
   return 0;
 }
@@ -169,20 +142,15 @@ static int pphase0(SacPlan& p, int flags, hipStream_t s) {
 static int pphase1(SacPlan& p, int flags, hipStream_t s) {
   const oac_sac_config& c = p.c;
   const oac_sac_layout& L = p.L;
-  const int B = c.batch, H = c.hidden, Do = c.obs_dim, Da = c.act_dim, RS = c.row_stride;
-  const int K = c.q_out, Dq = Do + Da;
+  const int B = c.batch, H = c.hidden, RS = c.row_stride, K = c.q_out;
   float* X = p.W(OAC_WS_BATCH);
   const float* q = p.b.params + L.q1_base;
   const float* tq = p.b.targets;
   {  // target critic layer 1 (its layer 0 finished in the head launch)
     GemmBatch gb{};
-    add(gb, t_fwd(p.W(X_H1T), H, B, H, tq + L.q_fc1_w, H, H, p.W(X_H2T), H, EPI_BIAS_RELU, tq + L.q_fc1_b));
-    if (p.direct_big) {   // the direct-gather step's batch copy: 256 tiles, a free slot per CU
-      RowGather& g = gb.rg;
-      g.ring = p.direct_ring; g.slots = p.b.ring_slots; g.B = B; g.state = p.state();
-      g.replay = p.b.replay; g.row_stride = RS; g.out = X;
-      g.blocks = 256;
-    }
+    add(gb, critic_l1(p, tq, X_H1T, X_H2T));
+    // the direct-gather step's batch copy: 256 tiles, a free slot per CU
+    if (p.direct_big) side_batch_copy(p, gb, p.direct_ring, X, 256);
     if (run_gemm(p, gb, s)) return 1;
   }
   {  // the target critic's K-output last layer runs inside the targets kernel (row_heads)
@@ -197,40 +165,27 @@ static int pphase1(SacPlan& p, int flags, hipStream_t s) {
     a.dq = p.W(X_DQ); a.sqe = p.W(OAC_WS_SQE1); a.y = p.W(OAC_WS_Y);
     a.counts = (flags & OAC_STEP_COUNTS) ? p.W(OAC_WS_COUNTS) : nullptr;
     a.loss_scale = 1.f; a.soft_prob = -1.f; a.rescale_spread = 0.f;   // particle_trainer_oac.py
-    TIMED(p, K_ROW, s, OAC_HIP_CHECK(launch_particle_targets(a, s)));
-    p.launches++;
+    RUN_ROW(p, s, launch_particle_targets(a, s));
   }
   // last layer: dW_last slab and dh2 = (dq . W_last) * [h2 > 0]; with dh2
   // from the targets kernel, dW_last rides in the layer-0 dW launch
   const bool fold = dh2_in_targets(p);
-  GemmTask tl;
-  {
-    float* gq = grad_q(p);
-    tl = t_dw(p.W(X_DQ), K, K, B, p.W(X_H2Q), H, H, gq + L.q_last_w, gq + L.q_last_b,
-              q_group(p), p.sp_ql);
-    // train_bias=False: no ones column, the frozen bias keeps a zero gradient
-    // (Adam then leaves it, and its moments, exactly unchanged)
-    if (c.freeze_q_bias) { tl.N = H; tl.b_ones = 0; tl.bias_grad = nullptr; }
-  }
+  const GemmTask tl = critic_last_dw(p, X_DQ, X_H2Q);
   if (!fold) {
     GemmBatch gb{};
     add(gb, tl);
-    add(gb, t_dx(p.W(X_DQ), K, B, K, q + L.q_last_w, H, H, p.W(X_DH2Q), H, p.W(X_H2Q), H));
+    add(gb, critic_last_dx(p, X_DQ, X_DH2Q, X_H2Q));
     if (run_gemm(p, gb, s)) return 1;
   }
   {
     GemmBatch gb{};
-    float* gq = grad_q(p);
-    add(gb, t_dw(p.W(X_DH2Q), H, H, B, p.W(X_H1Q), H, H, gq + L.q_fc1_w, gq + L.q_fc1_b,
-                 q_group(p), p.sp_q1));
-    add(gb, t_dx(p.W(X_DH2Q), H, B, H, q + L.q_fc1_w, H, H, p.W(X_DH1Q), H, p.W(X_H1Q), H));
+    add(gb, critic_l1_dw(p, X_DH2Q, X_H1Q));
+    add(gb, critic_l1_dx(p, X_DH2Q, X_DH1Q, X_H1Q));
     if (run_gemm(p, gb, s)) return 1;
   }
   {
     GemmBatch gb{};
-    float* gq = grad_q(p);
-    add(gb, t_dw(p.W(X_DH1Q), H, H, B, X + c.off_obs, RS, Dq, gq + L.q_fc0_w, gq + L.q_fc0_b,
-                 q_group(p), p.sp_q0));
+    add(gb, critic_l0_dw(p, X_DH1Q));
     // the last layer's dW (M = K rows) beside the layer-0 dW (B=4096: 7.9 us,
     // fewest workgroups of the backward launches; in the layer-1 launch it
     // added 5.8 us)
@@ -244,23 +199,17 @@ static int pphase1(SacPlan& p, int flags, hipStream_t s) {
 static int pphase2(SacPlan& p, hipStream_t s) {
   const oac_sac_config& c = p.c;
   const oac_sac_layout& L = p.L;
-  const int B = c.batch, H = c.hidden, Do = c.obs_dim, Da = c.act_dim, RS = c.row_stride;
-  const int K = c.q_out, Dq = Do + Da;
+  const int B = c.batch, H = c.hidden, Da = c.act_dim, K = c.q_out;
   float* X = p.W(OAC_WS_BATCH);
-  const float* pol = p.b.params;
   const float* q = p.b.params + L.q1_base;
   {
     GemmBatch gb{};
-    GemmTask t = t_fwd(X + c.off_obs, RS, B, Do, q + L.q_fc0_w, Dq, H, p.W(X_PN), H,
-                       EPI_BIAS_RANK_RELU, q + L.q_fc0_b);
-    t.U = p.W(OAC_WS_ACT1); t.ldu = Da; t.V = q + L.q_fc0_w + Do; t.ldv = Dq; t.R = Da;
-    t.C2 = p.W(X_H1N); t.ldc2 = H;
-    add(gb, t);
+    add(gb, critic_l0_rank(p, q, X + c.off_obs, p.W(OAC_WS_ACT1), Da, X_PN, X_H1N));
     if (run_gemm(p, gb, s)) return 1;
   }
   {
     GemmBatch gb{};
-    add(gb, t_fwd(p.W(X_H1N), H, B, H, q + L.q_fc1_w, H, H, p.W(X_H2N), H, EPI_BIAS_RELU, q + L.q_fc1_b));
+    add(gb, critic_l1(p, q, X_H1N, X_H2N));
     if (run_gemm(p, gb, s)) return 1;
   }
   {
@@ -274,24 +223,22 @@ static int pphase2(SacPlan& p, hipStream_t s) {
     a.target_entropy = c.target_entropy; a.lr = c.policy_lr; a.beta1 = c.beta1; a.beta2 = c.beta2;
     a.adam_eps = c.adam_eps; a.world_size = c.world_size;
     if (c.world_size > 1) { a.logp_part = p.W(OAC_WS_LOGP_PART); a.n_logp_part = (B + 15) / 16; }
-    TIMED(p, K_ROW, s, OAC_HIP_CHECK(launch_particle_min(a, s)));
-    p.launches++;
+    RUN_ROW(p, s, launch_particle_min(a, s));
   }
   if (H & 3) {   // (otherwise done by the min kernel)
     GemmBatch gb{};
-    add(gb, t_dx(p.W(X_GQ), K, B, K, q + L.q_last_w, H, H, p.W(X_DH2N), H, p.W(X_H2N), H));
+    add(gb, critic_last_dx(p, X_GQ, X_DH2N, X_H2N));
     if (run_gemm(p, gb, s)) return 1;
   }
   {
     GemmBatch gb{};
-    add(gb, t_dx(p.W(X_DH2N), H, B, H, q + L.q_fc1_w, H, H, p.W(X_DH1N), H, p.W(X_H1N), H));
+    add(gb, critic_l1_dx(p, X_DH2N, X_DH1N, X_H1N));
     if (run_gemm(p, gb, s)) return 1;
   }
   {  // dL/da through the critic's action columns + the tanh-Gaussian head
      // backward in the epilogue (EPI_HEAD_BWD, small kernel; one launch)
     GemmBatch gb{};
-    GemmTask t = t_dx(p.W(X_DH1N), H, B, H, q + L.q_fc0_w + Do, Dq, Da, p.W(X_DHEAD), 2 * Da,
-                      nullptr, 0);
+    GemmTask t = critic_act_dx(p, q, X_DH1N, X_DHEAD, 2 * Da);
     t.epi = EPI_HEAD_BWD;
     t.ex[0] = p.W(OAC_WS_ACT1); t.ex[1] = p.W(X_STD1); t.ex[2] = p.W(X_U1);
     t.ex[3] = p.W(OAC_WS_EPS2); t.ex[4] = p.W(OAC_WS_HEAD1);
@@ -301,31 +248,25 @@ static int pphase2(SacPlan& p, hipStream_t s) {
   }
   {
     GemmBatch gb{};
-    float* gp = grad_p(p);
-    add(gb, t_dw(p.W(X_DHEAD), 2 * Da, 2 * Da, B, p.W(X_H2P), H, H, gp + L.pol_head_w,
-                 gp + L.pol_head_b, L.pol_size, p.sp_ph));
-    add(gb, t_dx(p.W(X_DHEAD), 2 * Da, B, 2 * Da, pol + L.pol_head_w, H, H, p.W(X_DH2P), H, p.W(X_H2P), H));
+    add(gb, pol_head_dw(p, 0, X_DHEAD, X_H2P));
+    add(gb, pol_head_dx(p, 0, X_DHEAD, X_DH2P, X_H2P));
     if (run_gemm(p, gb, s)) return 1;
   }
   {
     GemmBatch gb{};
-    float* gp = grad_p(p);
-    add(gb, t_dw(p.W(X_DH2P), H, H, B, p.W(X_H1P), H, H, gp + L.pol_fc1_w, gp + L.pol_fc1_b,
-                 L.pol_size, p.sp_p1));
-    add(gb, t_dx(p.W(X_DH2P), H, B, H, pol + L.pol_fc1_w, H, H, p.W(X_DH1P), H, p.W(X_H1P), H));
+    add(gb, pol_l1_dw(p, 0, X_DH2P, X_H1P));
+    add(gb, pol_l1_dx(p, 0, X_DH2P, X_DH1P, X_H1P));
     if (run_gemm(p, gb, s)) return 1;
   }
   {
     GemmBatch gb{};
-    float* gp = grad_p(p);
-    add(gb, t_dw(p.W(X_DH1P), H, H, B, X + c.off_obs, RS, Do, gp + L.pol_fc0_w, gp + L.pol_fc0_b,
-                 L.pol_size, p.sp_p0));
+    add(gb, pol_l0_dw(p, 0, X_DH1P));
     if (run_gemm(p, gb, s)) return 1;
   }
   return 0;
 }
 
-int particle_run_step(SacPlan& p, int flags, hipStream_t s) {
+int particle_run_step(SacPlan& p, int flags, hipStream_t s, int, int) {
   p.launches = 0;
   if (pphase0(p, flags, s)) return 1;
   // One Adam launch per group here.  (Side-workgroup Adam, as the SAC step
@@ -336,49 +277,16 @@ int particle_run_step(SacPlan& p, int flags, hipStream_t s) {
   // update that layer while its gradient is still being written; the switch
   // that kept it for A/B runs is gone.)
   if (pphase1(p, flags, s)) return 1;
-  {
-    AdamArgs a = critic_adam(p, 0, nullptr);   // alpha is updated after the critic step
-    TIMED(p, K_ADAM, s, OAC_HIP_CHECK(launch_adam(a, s)));
-    p.launches++;
-  }
+  if (run_adam(p, critic_adam(p, 0, nullptr), s)) return 1;   // alpha is updated after the critic step
   if (pphase2(p, s)) return 1;
-  {
-    AdamArgs a = policy_adam(p, 0, p.c.auto_alpha ? p.alpha() : nullptr);
-    TIMED(p, K_ADAM, s, OAC_HIP_CHECK(launch_adam(a, s)));
-    p.launches++;
-  }
-  return 0;
+  return run_adam(p, policy_adam(p, 0, p.c.auto_alpha ? p.alpha() : nullptr), s);
 }
 
+// data-parallel split; the phase-3 policy Adam commits the alpha update
 int particle_step_phase(SacPlan& p, int phase, int flags, hipStream_t s) {
-  switch (phase) {
-    case 0: return pphase0(p, flags, s);
-    case 1:
-      if (pphase1(p, flags, s)) return 1;
-      if (p.S_q > 1) {
-        AdamArgs a = critic_adam(p, 1, nullptr);
-        OAC_HIP_CHECK(launch_adam(a, s));
-      }
-      return 0;
-    case 2: {
-      AdamArgs a = critic_adam(p, -1, nullptr);
-      OAC_HIP_CHECK(launch_adam(a, s));
-      if (pphase2(p, s)) return 1;
-      if (p.S_p > 1) {
-        AdamArgs b = policy_adam(p, 1, nullptr);
-        OAC_HIP_CHECK(launch_adam(b, s));
-      }
-      return 0;
-    }
-    case 3: {
-      AdamArgs a = policy_adam(p, -1, p.c.auto_alpha ? p.alpha() : nullptr);
-      OAC_HIP_CHECK(launch_adam(a, s));
-      return 0;
-    }
-    default:
-      set_error("bad phase %d", phase);
-      return 1;
-  }
+  return dp_step_phase(
+      p, phase, s, [&] { return pphase0(p, flags, s); }, [&] { return pphase1(p, flags, s); },
+      [&] { return pphase2(p, s); }, p.c.auto_alpha ? p.alpha() : nullptr);
 }
 
 }  // namespace oac

@@ -1,6 +1,8 @@
-// The plan object behind an oac_sac handle (SAC twin-critic and particle
-// K-head trainers share it; each kind has its own workspace layout and
-// launch sequence).
+// The plan object behind an oac_sac handle (every trainer kind shares it; each
+// kind has its own workspace layout and launch sequence, reached through
+// KindOps), and the building blocks the kinds' plan files share: Adam
+// arguments, workspace layout, gather / RowGather fills, launch wrappers and
+// the GEMM task makers.
 #pragma once
 #include "../../include/oac_amd.h"
 #include <cstring>
@@ -173,26 +175,307 @@ inline bool big_direct_ok(const SacPlan& p) {
          p.c.off_act == p.c.off_obs + p.c.obs_dim;
 }
 
-// particle trainer (particle_plan.hip)
-void particle_layout_workspace(SacPlan& p);
-int particle_run_step(SacPlan& p, int flags, hipStream_t s);
-int particle_step_phase(SacPlan& p, int phase, int flags, hipStream_t s);
-void particle_plan_splits(SacPlan& p);
+// ------------------------------------------------------------- workspace
+// Start a layout: every buffer empty; the returned set(id, rows, cols) sizes one.
+inline auto begin_layout(SacPlan& p) {
+  for (int i = 0; i < kMaxWs; ++i) p.ws[i] = {0, 0, 0};
+  return [&p](int id, int64_t r, int64_t cl) { p.ws[id] = {0, r, cl}; };
+}
+// Finish it: the split-K gradient slabs of both groups, then the offsets.
+inline void finish_layout(SacPlan& p) {
+  if (p.S_q > 1) p.ws[WS_GSLAB_Q] = {0, p.S_q, q_group(p)};
+  if (p.S_p > 1) p.ws[WS_GSLAB_P] = {0, p.S_p, p_group(p)};
+  int64_t off = 0;
+  for (int i = 0; i < kMaxWs; ++i) {
+    p.ws[i].off = off;
+    off = al64(off + p.ws[i].rows * p.ws[i].cols);
+  }
+  p.L.workspace_floats = off + 64;   // tail pad: GEMM k-contiguous loads may read 7 floats past a row
+}
+
+// ------------------------------------------------------- launch wrappers
+// a timed, counted Adam launch; the data-parallel phases' are neither
+inline int run_adam(SacPlan& p, const AdamArgs& a, hipStream_t s) {
+  TIMED(p, K_ADAM, s, OAC_HIP_CHECK(launch_adam(a, s)));
+  p.launches++;
+  return 0;
+}
+inline int run_adam_untimed(const AdamArgs& a, hipStream_t s) {
+  OAC_HIP_CHECK(launch_adam(a, s));
+  return 0;
+}
+// a timed, counted row-kernel launch (head, targets, seeds, head backward)
+#define RUN_ROW(p, s, call)                       \
+  do {                                            \
+    TIMED(p, K_ROW, s, OAC_HIP_CHECK(call));      \
+    (p).launches++;                               \
+  } while (0)
+
+// ------------------------------------------------------ gather and counts
+// The step's gather launch into the batch buffer.  n_steps > 0: the SAC ring
+// form (the minibatches and eps of n_steps consecutive steps into slots
+// 0..n_steps-1); 0: one batch.  with_eps: draw the Philox eps when the step
+// asks for them (never for the deterministic plans).
+inline int step_gather(SacPlan& p, int flags, hipStream_t s, int n_steps, bool with_eps) {
+  const oac_sac_config& c = p.c;
+  const int B = c.batch, Da = c.act_dim;
+  GatherArgs g;
+  std::memset(&g, 0, sizeof(g));
+  g.replay = p.b.replay; g.row_stride = c.row_stride; g.idx = gather_idx(p, flags); g.ring_slots = p.b.ring_slots;
+  g.out = p.W(OAC_WS_BATCH); g.B = (flags & OAC_STEP_GATHER) ? B : 0;
+  if (n_steps > 0) { g.n_steps = n_steps; g.out_stride = (long)B * c.row_stride; g.eps_stride = (long)B * Da; }
+  if (with_eps && (flags & OAC_STEP_DEVICE_EPS)) {
+    g.eps1 = p.W(OAC_WS_EPS1); g.eps2 = p.W(OAC_WS_EPS2); g.n_eps = B * Da;
+  }
+  g.seed = c.seed; g.state = p.state();
+  TIMED(p, K_GATHER, s, OAC_HIP_CHECK(launch_gather(g, s)));
+  p.launches++;
+  return 0;
+}
+// ring path of a counts=True trainer: this draw's counts on the device
+inline int step_counts(SacPlan& p, int flags, hipStream_t s) {
+  if ((flags & (OAC_STEP_GATHER | OAC_STEP_COUNTS)) != (OAC_STEP_GATHER | OAC_STEP_COUNTS) || !p.b.counts)
+    return 0;
+  CountsStepArgs ca{p.b.counts, p.b.count_tags, p.b.count_epoch, gather_idx(p, flags), p.b.ring_slots,
+                    p.state(), p.c.batch, p.W(OAC_WS_COUNTS)};
+  TIMED(p, K_GATHER, s, OAC_HIP_CHECK(launch_counts_step(ca, s)));
+  p.launches++;
+  return 0;
+}
+
+// ------------------------------------------------------- RowGather fills
+// every task of gb reads its rows from the replay through the index slot of `ring`
+inline void rows_through_ring(SacPlan& p, GemmBatch& gb, const int* ring) {
+  for (int i = 0; i < gb.ntasks; ++i) gb.t[i].a_rows = 1;
+  RowGather& g = gb.rg;
+  g.ring = ring; g.slots = p.b.ring_slots; g.B = p.c.batch; g.state = p.state();
+}
+// `blocks` side workgroups of gb copy the step's rows into the batch buffer X
+inline void side_batch_copy(SacPlan& p, GemmBatch& gb, const int* ring, float* X, int blocks) {
+  RowGather& g = gb.rg;
+  g.ring = ring; g.slots = p.b.ring_slots; g.B = p.c.batch; g.state = p.state();
+  g.replay = p.b.replay; g.row_stride = p.c.row_stride; g.out = X;
+  g.blocks = blocks;
+}
+// `blocks` side workgroups of gb draw the step's Philox eps
+inline void side_eps(SacPlan& p, GemmBatch& gb, float* e1, float* e2, int blocks) {
+  RowGather& g = gb.rg;
+  g.state = p.state(); g.eps1 = e1; g.eps2 = e2; g.n_eps = p.c.batch * p.c.act_dim; g.seed = p.c.seed;
+  g.blocks = blocks;
+}
+// The small-batch direct step's layer-0 launch: rows through the ring, the
+// batch copy by a wave per row (>= 8 waves per workgroup).  inl: the staged
+// indices travel in the kernel arguments (never under capture: a captured
+// launch would replay this step's indices).
+inline void direct_rows(SacPlan& p, GemmBatch& gb, const int* ring, float* X, bool inl) {
+  rows_through_ring(p, gb, ring);
+  side_batch_copy(p, gb, ring, X, std::max(1, (p.c.batch + 7) / 8));
+  if (inl) gb.rg.inl = p.inline_rows;
+  gb.rg.seed = p.c.seed;
+}
+
+// ----------------------------------------------------------- task makers
+// Named after what they compute; workspace ids are arguments (each plan
+// keeps its own enum).  `pol` / `q` are parameter blocks (policy- / critic-
+// shaped: the parameters, the targets, a frozen next-action policy).
+
+// the step's first launch publishes its Adam constants
+inline void publish_step(SacPlan& p, GemmBatch& gb) {
+  gb.publish = p.state(); gb.pub_beta1 = p.c.beta1; gb.pub_beta2 = p.c.beta2;
+}
+// policy layer 0 on the rows' obs (or next_obs) columns x: h1 = relu(x W0^T + b0)
+inline GemmTask pol_l0(SacPlan& p, const float* pol, const float* x, int h1) {
+  const oac_sac_config& c = p.c;
+  return t_fwd(x, c.row_stride, c.batch, c.obs_dim, pol + p.L.pol_fc0_w, c.obs_dim, c.hidden, p.W(h1),
+               c.hidden, EPI_BIAS_RELU, pol + p.L.pol_fc0_b);
+}
+// policy layer 1: h2 = relu(h1 W1^T + b1)
+inline GemmTask pol_l1(SacPlan& p, const float* pol, int h1, int h2) {
+  const int B = p.c.batch, H = p.c.hidden;
+  return t_fwd(p.W(h1), H, B, H, pol + p.L.pol_fc1_w, H, H, p.W(h2), H, EPI_BIAS_RELU, pol + p.L.pol_fc1_b);
+}
+// critic layer 0 with the rank-Da continuation: the obs projection x W_obs^T +
+// b0 is kept in `pre`, h1 = relu(pre + u W_act^T) (u: the actions, ldu apart)
+inline GemmTask critic_l0_rank(SacPlan& p, const float* q, const float* x, const float* u, long ldu,
+                               int pre, int h1) {
+  const oac_sac_config& c = p.c;
+  const int H = c.hidden, Do = c.obs_dim, Da = c.act_dim, Dq = Do + Da;
+  GemmTask t = t_fwd(x, c.row_stride, c.batch, Do, q + p.L.q_fc0_w, Dq, H, p.W(pre), H,
+                     EPI_BIAS_RANK_RELU, q + p.L.q_fc0_b);
+  t.U = u; t.ldu = ldu; t.V = q + p.L.q_fc0_w + Do; t.ldv = Dq; t.R = Da;
+  t.C2 = p.W(h1); t.ldc2 = H;
+  return t;
+}
+// target critic projection of next_obs: pre = x W_obs^T + b0 (the head launch
+// adds the next actions' columns)
+inline GemmTask target_proj(SacPlan& p, const float* tq, const float* x, int pre) {
+  const oac_sac_config& c = p.c;
+  return t_fwd(x, c.row_stride, c.batch, c.obs_dim, tq + p.L.q_fc0_w, c.obs_dim + c.act_dim, c.hidden,
+               p.W(pre), c.hidden, EPI_BIAS, tq + p.L.q_fc0_b);
+}
+// plain critic layer 1: h2 = relu(h1 W1^T + b1)
+inline GemmTask critic_l1(SacPlan& p, const float* q, int h1, int h2) {
+  const int B = p.c.batch, H = p.c.hidden;
+  return t_fwd(p.W(h1), H, B, H, q + p.L.q_fc1_w, H, H, p.W(h2), H, EPI_BIAS_RELU, q + p.L.q_fc1_b);
+}
+// critic last layer as a product of its own: out = h2 W_last^T + b_last
+inline GemmTask critic_last(SacPlan& p, const float* q, int h2, int out) {
+  const int B = p.c.batch, H = p.c.hidden, K = p.c.q_out;
+  return t_fwd(p.W(h2), H, B, H, q + p.L.q_last_w, H, K, p.W(out), K, EPI_BIAS, q + p.L.q_last_b);
+}
+
+// Policy backward, for the policy block at `off` in the policy group (0, or
+// tpol_base): gradients into grad_p at the same offset.  The layer-0 dW reads
+// the step's batch (p.X(): slot 0 outside the SAC ring step).
+inline GemmTask pol_head_dw(SacPlan& p, long off, int dhead, int h2) {
+  const int B = p.c.batch, H = p.c.hidden, Da = p.c.act_dim;
+  float* g = grad_p(p) + off;
+  return t_dw(p.W(dhead), 2 * Da, 2 * Da, B, p.W(h2), H, H, g + p.L.pol_head_w, g + p.L.pol_head_b,
+              p_group(p), p.sp_ph);
+}
+inline GemmTask pol_head_dx(SacPlan& p, long off, int dhead, int dh2, int h2) {
+  const int B = p.c.batch, H = p.c.hidden, Da = p.c.act_dim;
+  return t_dx(p.W(dhead), 2 * Da, B, 2 * Da, p.P(off) + p.L.pol_head_w, H, H, p.W(dh2), H, p.W(h2), H);
+}
+inline GemmTask pol_l1_dw(SacPlan& p, long off, int dh2, int h1) {
+  const int B = p.c.batch, H = p.c.hidden;
+  float* g = grad_p(p) + off;
+  return t_dw(p.W(dh2), H, H, B, p.W(h1), H, H, g + p.L.pol_fc1_w, g + p.L.pol_fc1_b, p_group(p), p.sp_p1);
+}
+inline GemmTask pol_l1_dx(SacPlan& p, long off, int dh2, int dh1, int h1) {
+  const int B = p.c.batch, H = p.c.hidden;
+  return t_dx(p.W(dh2), H, B, H, p.P(off) + p.L.pol_fc1_w, H, H, p.W(dh1), H, p.W(h1), H);
+}
+inline GemmTask pol_l0_dw(SacPlan& p, long off, int dh1) {
+  const oac_sac_config& c = p.c;
+  float* g = grad_p(p) + off;
+  return t_dw(p.W(dh1), c.hidden, c.hidden, c.batch, p.X() + c.off_obs, c.row_stride, c.obs_dim,
+              g + p.L.pol_fc0_w, g + p.L.pol_fc0_b, p_group(p), p.sp_p0);
+}
+
+// Plain backward of a single critic (the parameters' critic block; gradients
+// into grad_q).  Last layer: dW from the K output seeds dq, dX into dh2.
+inline GemmTask critic_last_dw(SacPlan& p, int dq, int h2) {
+  const int B = p.c.batch, H = p.c.hidden, K = p.c.q_out;
+  float* gq = grad_q(p);
+  GemmTask t = t_dw(p.W(dq), K, K, B, p.W(h2), H, H, gq + p.L.q_last_w, gq + p.L.q_last_b, q_group(p),
+                    p.sp_ql);
+  // train_bias=False: no ones column, the frozen bias keeps a zero gradient
+  // (Adam then leaves it, and its moments, exactly unchanged)
+  if (p.c.freeze_q_bias) { t.N = H; t.b_ones = 0; t.bias_grad = nullptr; }
+  return t;
+}
+inline GemmTask critic_last_dx(SacPlan& p, int dq, int dh2, int h2) {
+  const int B = p.c.batch, H = p.c.hidden, K = p.c.q_out;
+  return t_dx(p.W(dq), K, B, K, p.P(p.L.q1_base) + p.L.q_last_w, H, H, p.W(dh2), H, p.W(h2), H);
+}
+inline GemmTask critic_l1_dw(SacPlan& p, int dh2, int h1) {
+  const int B = p.c.batch, H = p.c.hidden;
+  float* gq = grad_q(p);
+  return t_dw(p.W(dh2), H, H, B, p.W(h1), H, H, gq + p.L.q_fc1_w, gq + p.L.q_fc1_b, q_group(p), p.sp_q1);
+}
+inline GemmTask critic_l1_dx(SacPlan& p, int dh2, int dh1, int h1) {
+  const int B = p.c.batch, H = p.c.hidden;
+  return t_dx(p.W(dh2), H, B, H, p.P(p.L.q1_base) + p.L.q_fc1_w, H, H, p.W(dh1), H, p.W(h1), H);
+}
+inline GemmTask critic_l0_dw(SacPlan& p, int dh1) {   // input = [obs | act] contiguous in the row
+  const oac_sac_config& c = p.c;
+  float* gq = grad_q(p);
+  return t_dw(p.W(dh1), c.hidden, c.hidden, c.batch, p.X() + c.off_obs, c.row_stride,
+              c.obs_dim + c.act_dim, gq + p.L.q_fc0_w, gq + p.L.q_fc0_b, q_group(p), p.sp_q0);
+}
+// Width-1 critic (SAC, DDPG): the backward into its last hidden layer, dh2 =
+// seed (x) w_last (x) [h2 > 0], is never stored -- it is the rank-1 A operand of
+// the layer-1 dX (weights at qw: a critic block, or its shadow) ...
+inline GemmTask critic_rank1_dx(SacPlan& p, const float* qw, int seed, int h2, int dh1, int h1) {
+  const int B = p.c.batch, H = p.c.hidden;
+  GemmTask d = t_dx(nullptr, 0, B, H, qw + p.L.q_fc1_w, H, H, p.W(dh1), H, p.W(h1), H);
+  set_rank1(d, p.W(seed), qw + p.L.q_last_w, p.W(h2), H);
+  return d;
+}
+// ... and of the layer-1 dW into the critic's gradient block g.  fold (small
+// batch, unsplit): the layer-1 bias column and the last layer's dW = dq^T h2,
+// db = sum dq in the tiles of the first column block, which load dq and h2 as
+// the seed's factors anyway (GemmTask::fold)
+inline GemmTask critic_rank1_dw(SacPlan& p, const float* q, float* g, int dq, int h2, int h1, bool fold) {
+  const int B = p.c.batch, H = p.c.hidden;
+  GemmTask t = t_dw(nullptr, 0, H, B, p.W(h1), H, H, g + p.L.q_fc1_w, g + p.L.q_fc1_b, q_group(p), p.sp_q1);
+  set_rank1(t, p.W(dq), q + p.L.q_last_w, p.W(h2), H);
+  if (fold) {
+    t.N = H; t.b_ones = 0; t.fold = 1;   // bias_grad keeps the layer-1 bias gradient
+    t.C2 = g + p.L.q_last_w; t.ldc2 = (long)p.L.q_last_b - (long)p.L.q_last_w;
+  }
+  return t;
+}
+// dL/da: dh1 through the action columns of the critic block q's layer 0
+inline GemmTask critic_act_dx(SacPlan& p, const float* q, int dh1, int out, long ldo) {
+  const oac_sac_config& c = p.c;
+  return t_dx(p.W(dh1), c.hidden, c.batch, c.hidden, q + p.L.q_fc0_w + c.obs_dim, c.obs_dim + c.act_dim,
+              c.act_dim, p.W(out), ldo, nullptr, 0);
+}
+
+// ---------------------------------------------------- data-parallel phases
+// The particle and deterministic plans' split at the exchange points: phase
+// 1 leaves the critic gradients in the grads arena, phase 2 applies their
+// all-reduced mean and leaves the policy's, phase 3 applies those (commit:
+// the alpha update it commits, or null).  These Adam launches are not timed.
+template <class F0, class F1, class F2>
+inline int dp_step_phase(SacPlan& p, int phase, hipStream_t s, F0 phase0, F1 phase1, F2 phase2,
+                         AlphaState* commit) {
+  switch (phase) {
+    case 0: return phase0();
+    case 1:
+      if (phase1()) return 1;
+      return p.S_q > 1 ? run_adam_untimed(critic_adam(p, 1, nullptr), s) : 0;
+    case 2:
+      if (run_adam_untimed(critic_adam(p, -1, nullptr), s)) return 1;
+      if (phase2()) return 1;
+      return p.S_p > 1 ? run_adam_untimed(policy_adam(p, 1, nullptr), s) : 0;
+    case 3: return run_adam_untimed(policy_adam(p, -1, commit), s);
+    default:
+      set_error("bad phase %d", phase);
+      return 1;
+  }
+}
 
 // deterministic-policy trainers with a target_policy: g-oac GaussianTrainer and
 // the p-oac ParticleTrainer of particle_trainer.py (det_plan.hip)
 inline bool has_target_policy(int kind) {
   return kind == OAC_KIND_GAUSS || kind == OAC_KIND_PARTICLE_UB;
 }
-void det_layout_workspace(SacPlan& p);
-int det_run_step(SacPlan& p, int flags, hipStream_t s);
-int det_step_phase(SacPlan& p, int phase, int flags, hipStream_t s);
 
+// ---------------------------------------------------------------- kinds
+// What the C ABI (plan_api.hip) needs of a trainer kind: one table entry.
+struct KindOps {
+  void (*layout)(SacPlan&);                                      // workspace layout
+  int (*run_step)(SacPlan&, int flags, hipStream_t, int i, int n);   // step i of n, single process
+  int (*step_phase)(SacPlan&, int phase, int flags, hipStream_t);    // null: no data-parallel step
+  int (*ws_alias)(int which);                                    // public view id -> the layout's buffer
+  int shadow_ws;                                                 // shadow-weight buffer, or -1
+  bool split_phase1;   // step_phase has phases 4 / 5: phase 1 split around the alpha exchange
+};
+const KindOps& kind_ops(int kind);   // kind: validated (oac_sac_create / _query_layout)
+
+// SAC / OAC twin critics (sac_plan.hip)
+void sac_layout_workspace(SacPlan& p);
+int sac_run_step(SacPlan& p, int flags, hipStream_t s, int i, int n);
+int sac_step_phase(SacPlan& p, int phase, int flags, hipStream_t s);
+int sac_ws_alias(int which);
+int sac_shadow_ws();
+// particle trainer (particle_plan.hip)
+void particle_layout_workspace(SacPlan& p);
+int particle_run_step(SacPlan& p, int flags, hipStream_t s, int i, int n);
+int particle_step_phase(SacPlan& p, int phase, int flags, hipStream_t s);
+int particle_ws_alias(int which);
+// GAUSS / PARTICLE_UB (det_plan.hip); every public view is its own buffer
+void det_layout_workspace(SacPlan& p);
+int det_run_step(SacPlan& p, int flags, hipStream_t s, int i, int n);
+int det_step_phase(SacPlan& p, int phase, int flags, hipStream_t s);
 // DDPGTrainer: one critic, deterministic policy, no target_policy block
 // (ddpg_plan.hip); single-process only
 void ddpg_layout_workspace(SacPlan& p);
-int ddpg_run_step(SacPlan& p, int flags, hipStream_t s);
-int ddpg_ws_alias(int which);   // public view id -> the DDPG layout's buffer
-int ddpg_shadow_ws();           // workspace id of its shadow weights
+int ddpg_run_step(SacPlan& p, int flags, hipStream_t s, int i, int n);
+int ddpg_ws_alias(int which);
+int ddpg_shadow_ws();
 
 }  // namespace oac

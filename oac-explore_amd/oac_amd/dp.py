@@ -20,7 +20,7 @@ single-process step on the union of the ranks' batches (tests/test_dp.py
 checks this with the CPU oracle over gloo).
 
 The exchanges are issued by liboac_amd itself, between its own launches
-(``oac_sac_set_allreduce``, sac_plan.hip ``run_step_dp``): over RCCL through
+(``oac_sac_set_allreduce``, plan_api.hip ``run_step_dp``): over RCCL through
 the library's own communicator (``oac_rccl_*``, bootstrapped from the process
 group; the nccl backend) or, over gloo, through a host callback into
 torch.distributed (tests).  A step is then one library call of direct

@@ -13,7 +13,7 @@ optimizers (state_dict-compatible views) and ``deterministic``.
 State lives in flat HBM arenas (params / grads / Adam m, v / targets); the
 modules exposed as ``policy``, ``qf1``, ... are views into them.  One step is
 one replay of a captured hipGraph of the HIP kernels (see
-csrc/sac_plan.hip); nothing of the step runs in torch.
+csrc/sac_plan.hip; the capture: csrc/plan_api.hip); nothing of the step runs in torch.
 """
 import ctypes
 from collections import OrderedDict

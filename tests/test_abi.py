@@ -64,6 +64,41 @@ def test_param_layout_matches_reference_parameter_counts(dims):
     assert lay.workspace_floats > 0
 
 
+@pytest.mark.parametrize("kind,q_out", [(0, 1), (1, 10), (2, 2), (3, 10), (4, 1)])
+def test_every_kind_has_a_layout_and_its_views_fit_the_workspace(kind, q_out):
+    """The per-kind table behind the handle (csrc/plan_api.hip kind_ops): each
+    trainer kind lays out a workspace, and every public view of a handle of
+    that kind lies inside it.  Host-only: with null buffers create makes no
+    GPU call."""
+    from oac_amd import _lib, row_layout
+    L = _lib.lib()
+    cfg = _lib.SacConfig()
+    cfg.kind, cfg.obs_dim, cfg.act_dim, cfg.hidden, cfg.q_out, cfg.batch = kind, 11, 3, 32, q_out, 40
+    for k, v in row_layout(11, 3).items():
+        setattr(cfg, k, v)
+    cfg.gemm_cfg = -1
+    cfg.world_size = 1
+    lay = _lib.SacLayout()
+    assert L.oac_sac_query_layout(ctypes.byref(cfg), ctypes.byref(lay)) == 0, L.oac_last_error()
+    assert lay.n_critics == (2 if kind == 0 else 1) and lay.workspace_floats > 0
+    h = ctypes.c_void_p()
+    bufs = _lib.SacBuffers()
+    assert L.oac_sac_create(ctypes.byref(cfg), ctypes.byref(bufs), ctypes.byref(h)) == 0, L.oac_last_error()
+    try:
+        off, rows, cols = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
+        for name, which in _lib.WS.items():
+            assert L.oac_sac_workspace_view(h, which, ctypes.byref(off), ctypes.byref(rows),
+                                            ctypes.byref(cols)) == 0, name
+            assert off.value >= 0 and rows.value >= 0 and cols.value >= 0, name
+            assert off.value + rows.value * cols.value <= lay.workspace_floats, name
+        # the step's batch is a view of every layout
+        L.oac_sac_workspace_view(h, _lib.WS["batch"], ctypes.byref(off), ctypes.byref(rows),
+                                 ctypes.byref(cols))
+        assert (rows.value, cols.value) == (40, cfg.row_stride)
+    finally:
+        assert L.oac_sac_destroy(h) == 0
+
+
 def test_row_layout_keeps_critic_input_contiguous():
     from oac_amd import row_layout
     r = row_layout(376, 17)

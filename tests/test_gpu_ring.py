@@ -1,6 +1,6 @@
 """Device-resident ring path (SACTrainer.train_from_ring): the minibatches of
 up to 8 consecutive steps are gathered by one launch at the start of an
-n-step graph (csrc/sac_plan.hip, gather_steps); the result must not depend on
+n-step graph (csrc/sac_plan.h, step_gather); the result must not depend on
 how the steps are split into calls -- one call of 16 steps (two batched
 gathers), two calls of 8, sixteen calls of 1 are bitwise equal."""
 import numpy as np
