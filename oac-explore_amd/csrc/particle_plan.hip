@@ -83,6 +83,7 @@ static int pphase0(SacPlan& p, int flags, hipStream_t s) {
   // critic's layer-1 launch -- no gather launch
   const bool direct_big = big_direct_ok(p) && (flags & OAC_STEP_GATHER) && p.b.ring_slots > 0;
   p.direct_big = direct_big;
+  if (direct_big) p.trace |= OAC_TRACE_DIRECT_BIG;
   p.direct_ring = gather_idx(p, flags);
   const float* R0 = direct_big ? p.b.replay : X;
   const float* obs = R0 + c.off_obs;

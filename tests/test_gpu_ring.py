@@ -14,7 +14,7 @@ pytestmark = pytest.mark.gpu
 Do, Da, H, B = 11, 3, 32, 32
 
 
-def _trainer():
+def _trainer(Do=Do, Da=Da, H=H):
     from gpu_helpers import producers, Space
     from oac_amd import SACTrainer
     pp, qp = producers(sac_params(Do, Da, [H, H], 3, pi_init_w=0.2, q_init_w=0.1))
@@ -23,7 +23,7 @@ def _trainer():
                       use_automatic_entropy_tuning=True)
 
 
-def _run(splits):
+def _run(splits, Do=Do, Da=Da, H=H, B=B):
     from oac_amd import DeviceIndexStream, ReplayBuffer
     from gpu_helpers import Space
     rb = ReplayBuffer(2000, Space(Do), Space(Da), device="cuda:0")
@@ -32,7 +32,7 @@ def _run(splits):
         data["observations"], data["actions"], data["rewards"], data["next_observations"],
         data["terminals"])).cuda())
     st = DeviceIndexStream(rb, B, chunk=16, seed=4)
-    tr = _trainer()
+    tr = _trainer(Do, Da, H)
     for n in splits:
         st.before_step(n)
         tr.train_from_ring(rb._storage, st.ring, st.slots, B, n_steps=n)
@@ -49,8 +49,14 @@ def test_ring_steps_independent_of_call_split():
     np.testing.assert_array_equal(a, c)
 
 
-@pytest.mark.parametrize("prefetch", [0, 1])
-def test_ring_direct_rows_equal_the_gather_launch_path(prefetch):
+# (7, 5, 32, 37): n_eps = 185 per step, so the gather launch's eps waves of
+# 2, 4, 8 and 16 (two gathers of 8) steps never end on a wave boundary, the
+# Box-Muller pairs straddle rows (odd Da) and steps (odd n_eps), and the 37
+# gather rows of a step end mid workgroup
+@pytest.mark.parametrize("prefetch,shape", [(0, (Do, Da, H, B)), (1, (Do, Da, H, B)),
+                                            (0, (7, 5, 32, 37)), (1, (7, 5, 32, 37))],
+                         ids=["0", "1", "0-b37", "1-b37"])
+def test_ring_direct_rows_equal_the_gather_launch_path(prefetch, shape):
     """The small-batch ring step's default form -- layer 0 reading its rows
     through the device index ring, side blocks copying the batch and drawing
     eps (the drop-in step's form) -- against the gather launch per 8 steps
@@ -62,9 +68,9 @@ def test_ring_direct_rows_equal_the_gather_launch_path(prefetch):
     from oac_amd import _lib
     try:
         _lib.set_tuning(head_dh2=-1 if prefetch else 0)
-        a = _run([16, 8, 4, 2, 1, 1])
+        a = _run([16, 8, 4, 2, 1, 1], *shape)
         _lib.set_tuning(ring_direct=-1, ring_prefetch=prefetch)
-        b = _run([16, 8, 4, 2, 1, 1])
+        b = _run([16, 8, 4, 2, 1, 1], *shape)
     finally:
         _lib.set_tuning(ring_direct=0, ring_prefetch=0, head_dh2=0)
     assert np.isfinite(a).all()
