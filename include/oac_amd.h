@@ -65,7 +65,7 @@ typedef struct oac_sac_config {
                             OAC_KIND_GAUSS (one critic, q_out=2: mean | log std);
                             OAC_KIND_DDPG (one critic, q_out=1) */
   int obs_dim, act_dim;
-  int hidden;            /* width of both hidden layers (reference: [M]*N, N=2) */
+  int hidden;            /* width of every hidden layer (reference: [M]*N; N = n_hidden) */
   int q_out;             /* 1 for SAC/OAC; K heads for the shared-layer particle critic */
   int batch;             /* per-rank batch size */
   float discount, reward_scale, tau;
@@ -92,6 +92,12 @@ typedef struct oac_sac_config {
   /* PARTICLE, PARTICLE_UB, GAUSS: train_bias=False (networks.py:59-60: the critic's
    * last_fc.bias has requires_grad=False, so it is never updated) */
   int freeze_q_bias;
+  /* hidden layers of the policy and of the critic: 0 (a zero-initialised
+   * config) or 2 = the two-layer networks; 1 = one hidden layer, for
+   * OAC_KIND_GAUSS and OAC_KIND_PARTICLE_UB only (main.py's --num_layers 1
+   * default, the riverswim recipes).  At 1 the layout has no fc1 tensors:
+   * pol_fc1_* and q_fc1_* are -1; hidden must then be a multiple of 4 */
+  int n_hidden;
 } oac_sac_config;
 
 /* Flat parameter arena layout (float offsets; every tensor 16-byte aligned).
@@ -399,7 +405,9 @@ int oac_expl_set_ub_index(oac_expl* h, int index);
  * workgroup per (row, network).  offsets = {fc0.weight, fc0.bias, fc1.weight,
  * fc1.bias, last_fc.weight, last_fc.bias} inside each parameter block
  * (oac_sac_layout q_* or pol_* fields; the policy's last_fc is the stacked
- * [2*act_dim, hidden] head).
+ * [2*act_dim, hidden] head).  offsets[2] = -1 (a depth-1 layout's fc1 fields;
+ * offsets[3] is then not read): a one-hidden-layer network, the last layer and
+ * the Jacobian start from layer 0's activations.
  * oac_critic_eval: FlattenMlp(obs, act) (networks.py:154-161) of n_nets (1 or 2)
  * critic blocks -> q [n, n_nets*q_out]; jac (optional) [n, n_nets*q_out,
  * obs_dim+act_dim] = d q / d [obs | act], for SACTrainer.predict /

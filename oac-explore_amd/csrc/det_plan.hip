@@ -29,6 +29,17 @@
 // before either policy loss is formed.  The two policy losses are independent
 // (pi's step touches neither Q nor piT), so their backward passes share
 // launches, and one Adam pass updates [policy | target_policy].
+//
+// One hidden layer (n_hidden == 1, main.py's --num_layers 1 default: the
+// riverswim recipes): the layer-0 activations take the place of h2 everywhere
+// (the head launch, the row kernels' RowHeads), the layer-1 products are gone,
+// and what two-layer steps do in GEMM launches between the row kernels is per-row
+// work those kernels take over: the critic's own last layer and its backward
+// into the hidden layer run inside the targets kernel (qh / dh2), so the last
+// layer's and layer 0's dW share one launch with the critic's Adam; and one row
+// kernel (det_seed_head_backward_kernel) carries both policy losses from the
+// post-step critic's hidden activations to the policy heads' gradients.
+// Launches beyond gather / counts: 2 + 2 + 4 = 8 (two layers: 18).
 #include <cstring>
 
 #include "../../include/oac_amd.h"
@@ -77,6 +88,8 @@ void det_layout_workspace(SacPlan& p) {
 
 // ------------------------------------------------------------------ phases
 // forward of everything the pre-step parameters determine
+static inline bool shallow(const SacPlan& p) { return p.c.n_hidden == 1; }
+
 static int dphase0(SacPlan& p, int flags, hipStream_t s) {
   const oac_sac_config& c = p.c;
   const oac_sac_layout& L = p.L;
@@ -104,7 +117,8 @@ static int dphase0(SacPlan& p, int flags, hipStream_t s) {
     add(gb, target_proj(p, tq, nobs, G_PT));
     if (run_gemm(p, gb, s)) return 1;
   }
-  {
+  const bool sh = shallow(p);
+  if (!sh) {
     GemmBatch gb{};
     add(gb, pol_l1(p, pol, G_H1P, G_H2P));
     add(gb, pol_l1(p, npol, G_H1P2, G_H2P2));
@@ -120,14 +134,14 @@ static int dphase0(SacPlan& p, int flags, hipStream_t s) {
     a.B = B; a.H = H; a.Da = Da;
     a.col_chunks = std::max(1, (H + (B >= 1024 ? 127 : 63)) / (B >= 1024 ? 128 : 64));
     HeadSeg& s0 = a.seg[0];   // policy(obs) -> a~ (post-step critic, phase 2)
-    s0.h2 = p.W(G_H2P); s0.wh = pol + L.pol_head_w; s0.bh = pol + L.pol_head_b;
+    s0.h2 = p.W(sh ? G_H1P : G_H2P); s0.wh = pol + L.pol_head_w; s0.bh = pol + L.pol_head_b;
     s0.head = p.W(OAC_WS_HEAD1); s0.act = p.W(OAC_WS_ACT1);
     HeadSeg& s1 = a.seg[1];   // next-action policy(next_obs) -> QT(next_obs, a')
-    s1.h2 = p.W(G_H2P2); s1.wh = npol + L.pol_head_w; s1.bh = npol + L.pol_head_b;
+    s1.h2 = p.W(sh ? G_H1P2 : G_H2P2); s1.wh = npol + L.pol_head_w; s1.bh = npol + L.pol_head_b;
     s1.head = p.W(OAC_WS_HEAD2); s1.act = p.W(OAC_WS_ACT2);
     s1.n_nets = 1; s1.wa[0] = tq + L.q_fc0_w + Do; s1.pre[0] = p.W(G_PT); s1.h1[0] = p.W(G_H1T);
     HeadSeg& s2 = a.seg[2];   // target_policy(obs) -> a~_T (phase 2)
-    s2.h2 = p.W(G_H2TP); s2.wh = tpol + L.pol_head_w; s2.bh = tpol + L.pol_head_b;
+    s2.h2 = p.W(sh ? G_H1TP : G_H2TP); s2.wh = tpol + L.pol_head_w; s2.bh = tpol + L.pol_head_b;
     s2.head = p.W(OAC_WS_HEAD3); s2.act = p.W(OAC_WS_ACT3);
     RUN_ROW(p, s, launch_policy_head(a, 3, s));
   }
@@ -142,7 +156,8 @@ static int dphase1(SacPlan& p, int flags, hipStream_t s, bool fused) {
   float* X = p.W(OAC_WS_BATCH);
   const float* q = p.b.params + L.q1_base;
   const float* tq = p.b.targets;
-  {  // target critic layer 1, and the critic's outputs Q(obs, a)
+  const bool sh = shallow(p);
+  if (!sh) {  // target critic layer 1, and the critic's outputs Q(obs, a)
     GemmBatch gb{};
     add(gb, critic_l1(p, tq, G_H1T, G_H2T));
     add(gb, critic_last(p, q, G_H2Q, OAC_WS_Q1));
@@ -150,7 +165,14 @@ static int dphase1(SacPlan& p, int flags, hipStream_t s, bool fused) {
   }
   // the target critic's K-output last layer runs inside the targets kernel
   // (row_heads, rows.hip): one launch fewer on the chain
-  const RowHead th{p.W(G_H2T), tq + L.q_last_w, tq + L.q_last_b, p.W(OAC_WS_TQ1), H};
+  const RowHead th{p.W(sh ? G_H1T : G_H2T), tq + L.q_last_w, tq + L.q_last_b, p.W(OAC_WS_TQ1), H};
+  // one hidden layer: Q(obs, a)'s last layer too, and its backward into the
+  // hidden layer, dh1q = [h1q > 0] (dq . W_last) (float4 columns: H % 4 == 0,
+  // checked when the plan is created)
+  RowHead qh;
+  std::memset(&qh, 0, sizeof(qh));
+  if (sh) qh = RowHead{p.W(G_H1Q), q + L.q_last_w, q + L.q_last_b, p.W(OAC_WS_Q1), H};
+  float* dh_out = sh ? p.W(G_DH1Q) : nullptr;
   const float* counts = (flags & OAC_STEP_COUNTS) ? p.W(OAC_WS_COUNTS) : nullptr;
   if (c.kind == OAC_KIND_GAUSS) {
     GaussTargetArgs a;
@@ -159,7 +181,7 @@ static int dphase1(SacPlan& p, int flags, hipStream_t s, bool fused) {
     a.off_rew = c.off_rew; a.off_term = c.off_term; a.reward_scale = c.reward_scale;
     a.discount = c.discount; a.std_init = c.std_init;
     a.soft_prob = c.std_soft_update ? c.std_soft_prob : -1.f;
-    a.counts = counts; a.th = th;
+    a.counts = counts; a.th = th; a.qh = qh; a.dh2 = dh_out;
     a.B = B; a.dq = p.W(G_DQ); a.y = p.W(OAC_WS_Y); a.sqe = p.W(OAC_WS_SQE1);
     RUN_ROW(p, s, launch_gauss_targets(a, s));
   } else {
@@ -169,10 +191,23 @@ static int dphase1(SacPlan& p, int flags, hipStream_t s, bool fused) {
     a.off_rew = c.off_rew; a.off_term = c.off_term; a.reward_scale = c.reward_scale;
     a.discount = c.discount; a.B = B; a.K = K;
     a.dq = p.W(G_DQ); a.sqe = p.W(OAC_WS_SQE1); a.y = p.W(OAC_WS_Y); a.counts = counts; a.th = th;
+    a.qh = qh; a.dh2 = dh_out;
     a.loss_scale = 1.f / (float)K;                       // qf_loss /= num_particles
     a.soft_prob = c.std_soft_update ? c.std_soft_prob : -1.f;
     a.rescale_spread = c.rescale_spread;
     RUN_ROW(p, s, launch_particle_targets(a, s));
+  }
+  if (sh) {   // both weight gradients in one launch
+    GemmBatch gb{};
+    add(gb, critic_last_dw(p, G_DQ, G_H1Q));
+    add(gb, critic_l0_dw(p, G_DH1Q));
+    if (fused) {   // critic Adam + Polyak in the tiles' epilogues; a tail block for what no
+                   // tile covers: a frozen last-layer bias (zero gradient; Polyak still applies)
+      const long off[1] = {(long)L.q_last_b};
+      const long n[1] = {(long)(L.q_size - L.q_last_b)};
+      fuse_adam(gb, critic_adam(p, 0, nullptr), c.freeze_q_bias ? 1 : 0, off, n);
+    }
+    return run_gemm(p, gb, s);
   }
   {
     GemmBatch gb{};
@@ -212,6 +247,39 @@ static int dphase2(SacPlan& p, hipStream_t s, bool fused) {
     add(gb, critic_l0_rank(p, q, X + c.off_obs, p.W(OAC_WS_ACT1), Da, G_PN, G_H1N));
     add(gb, critic_l0_rank(p, q, X + c.off_obs, p.W(OAC_WS_ACT3), Da, G_PN3, G_H1N3));
     if (run_gemm(p, gb, s)) return 1;
+  }
+  const long tp = L.tpol_base;   // the target_policy block's offset in the policy group
+  if (shallow(p)) {
+    {
+      DetSeedHeadBwdArgs a;
+      std::memset(&a, 0, sizeof(a));
+      a.hn = RowHead{p.W(G_H1N), q + L.q_last_w, q + L.q_last_b, p.W(OAC_WS_QN1), H};
+      a.h1n1 = p.W(G_H1N3);
+      a.wa = q + L.q_fc0_w + c.obs_dim; a.ld_wa = c.obs_dim + Da;
+      a.act[0] = p.W(OAC_WS_ACT1); a.dhead[0] = p.W(G_DHEAD);
+      a.act[1] = p.W(OAC_WS_ACT3); a.dhead[1] = p.W(G_DHEAD3);
+      a.ub = p.W(OAC_WS_QNEW);
+      a.gauss = c.kind == OAC_KIND_GAUSS; a.std_bound = c.std_bound; a.delta_index = c.delta_index;
+      a.B = B; a.K = K; a.Da = Da;
+      RUN_ROW(p, s, launch_det_seed_head_backward(a, s));
+    }
+    {
+      GemmBatch gb{};
+      add(gb, pol_head_dw(p, 0, G_DHEAD, G_H1P));
+      add(gb, pol_head_dx(p, 0, G_DHEAD, G_DH1P, G_H1P));
+      add(gb, pol_head_dw(p, tp, G_DHEAD3, G_H1TP));
+      add(gb, pol_head_dx(p, tp, G_DHEAD3, G_DH1TP, G_H1TP));
+      if (run_gemm(p, gb, s)) return 1;
+    }
+    GemmBatch gb{};
+    add(gb, pol_l0_dw(p, 0, G_DH1P));
+    add(gb, pol_l0_dw(p, tp, G_DH1TP));
+    if (fused) {   // [policy | target_policy] Adam in the epilogue; tail blocks: the heads
+      const long off[2] = {(long)L.pol_head_w, (long)(L.tpol_base + L.pol_head_w)};
+      const long n[2] = {(long)(L.pol_size - L.pol_head_w), (long)(L.pol_size - L.pol_head_w)};
+      fuse_adam(gb, policy_adam(p, 0, nullptr), 2, off, n);
+    }
+    return run_gemm(p, gb, s);
   }
   {
     GemmBatch gb{};
@@ -264,7 +332,6 @@ static int dphase2(SacPlan& p, hipStream_t s, bool fused) {
     a.nseg = 2; a.B = B; a.act_dim = Da;
     RUN_ROW(p, s, launch_det_head_backward(a, s));
   }
-  const long tp = L.tpol_base;   // the target_policy block's offset in the policy group
   {
     GemmBatch gb{};
     add(gb, pol_head_dw(p, 0, G_DHEAD, G_H2P));

@@ -305,6 +305,28 @@ struct ParticleUbSeedArgs {            // particle_trainer.py:317-330, :339-348
 };
 hipError_t launch_particle_ub_seed(const ParticleUbSeedArgs& a, hipStream_t s);
 
+// One-hidden-layer critics (det_plan.hip, n_hidden == 1): both policy losses'
+// backward from the post-step critic's hidden activations to the policy heads
+// in one launch.  Segment 0 = policy, 1 = target_policy; per row of segment s
+//   qn = h1n[s] W_last^T + b_last                    (segment 0 only: row_heads, -> QN1)
+//   g  = the seed of gauss_seed_kernel / particle_ub_seed_kernel (K <= 2: GAUSS
+//        when gauss != 0; segment 1's seed is a constant), ub -> QNEW
+//   dh1[n]   = [h1n[s][r, n] > 0] sum_k g[k] W_last[k, n]
+//   da[j]    = sum_n dh1[n] wa[n, j]                 (wa = W0[:, Do:], row n at wa + n ld_wa)
+//   dhead[j] = da[j] (1 - a_s[r, j]^2),  dhead[Da + j] = 0
+// replacing the seed, critic_last_dx, critic_act_dx and det_head_backward launches.
+struct DetSeedHeadBwdArgs {
+  RowHead hn;                           // h = h1n[0], W_last, b_last, out = QN1; H
+  const float* h1n1;                    // [B, H] h1n[1]
+  const float* wa; long ld_wa;          // the post-step critic's action columns
+  const float* act[2]; float* dhead[2]; // [B, Da], [B, 2 Da]
+  float* ub;                            // [B] upper bound (QNEW)
+  int gauss; float std_bound;           // GAUSS: q + std_bound exp(log std)
+  int delta_index;                      // PARTICLE_UB: the sorted particle maximised
+  int B, K, Da;
+};
+hipError_t launch_det_seed_head_backward(const DetSeedHeadBwdArgs& a, hipStream_t s);
+
 struct DetHeadBwdArgs {                 // d tanh(mean): dmean = da (1 - a^2), d log std = 0
   const float* da[2]; const float* act[2]; float* dhead[2];
   int nseg, B, act_dim;

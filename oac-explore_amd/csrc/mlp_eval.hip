@@ -38,13 +38,17 @@ __device__ __forceinline__ void dense_rows(const float* W, const float* b, const
   }
 }
 
-// the shared trunk: x (LDS, n_in) -> h0, h1 (LDS, H each)
-__device__ __forceinline__ void trunk(const float* net, const MlpEvalArgs& a, const float* x,
-                                      int n_in, float* h0, float* h1) {
+// the shared trunk: x (LDS, n_in) -> h0, h1 (LDS, H each); returns the last
+// hidden layer's activations: h1, or h0 for a one-hidden-layer network
+// (a.w1 < 0: no layer 1)
+__device__ __forceinline__ const float* trunk(const float* net, const MlpEvalArgs& a, const float* x,
+                                              int n_in, float* h0, float* h1) {
   dense_rows(net + a.w0, net + a.b0, x, n_in, a.H, h0, true);
   __syncthreads();
+  if (a.w1 < 0) return h0;
   dense_rows(net + a.w1, net + a.b1, h0, a.H, a.H, h1, true);
   __syncthreads();
+  return h1;
 }
 
 __device__ __forceinline__ void load_input(const MlpEvalArgs& a, int row, float* x) {
@@ -66,8 +70,8 @@ __global__ void __launch_bounds__(256) critic_eval_kernel(MlpEvalArgs a) {
   float* q = g2 + H;
   const float* net = a.net[ni];
   load_input(a, row, x);
-  trunk(net, a, x, din, h0, h1);
-  dense_rows(net + a.wl, net + a.bl, h1, H, a.Q, q, false);
+  const float* hl = trunk(net, a, x, din, h0, h1);
+  dense_rows(net + a.wl, net + a.bl, hl, H, a.Q, q, false);
   __syncthreads();
   for (int k = threadIdx.x; k < a.Q; k += blockDim.x)
     a.out[(long)row * a.ld_out + ni * a.Q + k] = q[k];
@@ -75,13 +79,18 @@ __global__ void __launch_bounds__(256) critic_eval_kernel(MlpEvalArgs a) {
   const float* W1 = net + a.w1;
   const float* W0 = net + a.w0;
   for (int k = 0; k < a.Q; ++k) {
-    for (int j = threadIdx.x; j < H; j += blockDim.x)
-      g2[j] = h1[j] > 0.f ? net[a.wl + (long)k * H + j] : 0.f;
-    __syncthreads();
-    for (int i = threadIdx.x; i < H; i += blockDim.x) {
-      float s = 0.f;
-      for (int j = 0; j < H; ++j) s = fmaf(g2[j], W1[(long)j * H + i], s);
-      g1[i] = h0[i] > 0.f ? s : 0.f;
+    if (a.w1 < 0) {   // one hidden layer: the Jacobian starts from h0
+      for (int j = threadIdx.x; j < H; j += blockDim.x)
+        g1[j] = h0[j] > 0.f ? net[a.wl + (long)k * H + j] : 0.f;
+    } else {
+      for (int j = threadIdx.x; j < H; j += blockDim.x)
+        g2[j] = h1[j] > 0.f ? net[a.wl + (long)k * H + j] : 0.f;
+      __syncthreads();
+      for (int i = threadIdx.x; i < H; i += blockDim.x) {
+        float s = 0.f;
+        for (int j = 0; j < H; ++j) s = fmaf(g2[j], W1[(long)j * H + i], s);
+        g1[i] = h0[i] > 0.f ? s : 0.f;
+      }
     }
     __syncthreads();
     float* out = a.jac + ((long)row * a.n_nets * a.Q + (long)ni * a.Q + k) * din;
@@ -108,8 +117,8 @@ __global__ void __launch_bounds__(256) policy_eval_kernel(MlpEvalArgs a) {
   float* lp = hd + 2 * Da;   // [Da] per-dim log-prob terms
   const float* net = a.net[0];
   load_input(a, row, x);
-  trunk(net, a, x, din, h0, h1);
-  dense_rows(net + a.wl, net + a.bl, h1, H, a.p_fixed_std ? Da : 2 * Da, hd, false);
+  const float* hl = trunk(net, a, x, din, h0, h1);
+  dense_rows(net + a.wl, net + a.bl, hl, H, a.p_fixed_std ? Da : 2 * Da, hd, false);
   __syncthreads();
   if (a.p_fixed_std) {
     // std given (policies.py:244-249, 280-282): log_std = log(std), neither

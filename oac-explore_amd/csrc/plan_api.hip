@@ -37,16 +37,18 @@ static void compute_layout(const oac_sac_config& c, oac_sac_layout& L) {
   int64_t o = 0;
   L.pol_fc0_w = o; o = al4(o + H * Do);
   L.pol_fc0_b = o; o = al4(o + H);
-  L.pol_fc1_w = o; o = al4(o + H * H);
-  L.pol_fc1_b = o; o = al4(o + H);
+  // one hidden layer (n_hidden == 1): no fc1 tensors, offsets -1
+  const bool two = c.n_hidden != 1;
+  L.pol_fc1_w = two ? o : -1; if (two) o = al4(o + H * H);
+  L.pol_fc1_b = two ? o : -1; if (two) o = al4(o + H);
   L.pol_head_w = o; o = al4(o + 2 * Da * H);
   L.pol_head_b = o; o = al4(o + 2 * Da);
   L.pol_size = o;
   int64_t q = 0;
   L.q_fc0_w = q; q = al4(q + H * (Do + Da));
   L.q_fc0_b = q; q = al4(q + H);
-  L.q_fc1_w = q; q = al4(q + H * H);
-  L.q_fc1_b = q; q = al4(q + H);
+  L.q_fc1_w = two ? q : -1; if (two) q = al4(q + H * H);
+  L.q_fc1_b = two ? q : -1; if (two) q = al4(q + H);
   L.q_last_w = q; q = al4(q + Q * H);
   L.q_last_b = q; q = al4(q + Q);
   L.q_size = q;
@@ -188,6 +190,22 @@ static int validate(const oac_sac_config* c) {
     set_error("particle critic: 1 <= q_out <= 16 heads");
     return 1;
   }
+  if (c->n_hidden != 0 && c->n_hidden != 1 && c->n_hidden != 2) {
+    set_error("n_hidden must be 1 or 2 (0 = 2), got %d", c->n_hidden);
+    return 1;
+  }
+  if (c->n_hidden == 1 && !has_target_policy(c->kind)) {
+    static const char* const names[] = {"SAC", "PARTICLE", "GAUSS", "PARTICLE_UB", "DDPG"};
+    set_error("n_hidden = 1: kind %d (%s) has two-hidden-layer networks only; one hidden layer "
+              "is implemented for GAUSS (kind %d) and PARTICLE_UB (kind %d)",
+              c->kind, names[c->kind], OAC_KIND_GAUSS, OAC_KIND_PARTICLE_UB);
+    return 1;
+  }
+  if (c->n_hidden == 1 && (c->hidden & 3)) {
+    set_error("n_hidden = 1: hidden must be a multiple of 4 (the row kernels read the hidden "
+              "activations as float4 columns), got %d", c->hidden);
+    return 1;
+  }
   if (c->obs_dim < 1 || c->act_dim < 1 || c->act_dim > 32 || c->hidden < 1 || c->batch < 1) {
     set_error("bad dims obs=%d act=%d hidden=%d batch=%d", c->obs_dim, c->act_dim, c->hidden, c->batch);
     return 1;
@@ -249,6 +267,9 @@ static void plan_splits(SacPlan& p) {
       }
     if (forced) p.sp_ql = p.sp_q1;   // (only then: the plan's own sp_ql choice stands otherwise)
   }
+  // one hidden layer: a group's two dW products (layer 0, last layer / heads)
+  // share one launch and one split, so every slab of the group is written
+  if (c.n_hidden == 1) { p.sp_q1 = p.sp_ql = p.sp_q0; p.sp_p1 = p.sp_ph = p.sp_p0; }
   p.S_q = std::max(std::max(p.sp_q0.S, p.sp_q1.S), p.sp_ql.S);
   p.S_p = std::max(std::max(p.sp_p0.S, p.sp_p1.S), p.sp_ph.S);
 }

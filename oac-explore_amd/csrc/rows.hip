@@ -750,16 +750,26 @@ hipError_t launch_particle_min(const ParticleMinArgs& a, hipStream_t s) {
 //   q_target   = scale*r + (1-d)*gamma*tq0 ; std_target = clamp(., 0, std_init)
 //   loss = MSE(q0, q_target) + MSE(std, std_target)
 //   dL/dq0 = 2 (q0 - y_q) / B ;  dL/dq1 = 2 (std - y_s) / B * std  (exp backward)
-__global__ void __launch_bounds__(256) gauss_targets_kernel(GaussTargetArgs p) {
-  __shared__ RowHeadLds hs;
+__device__ __forceinline__ void gauss_targets_rows(const GaussTargetArgs& p, RowHeadLds& hs,
+                                                   RowHeadLds& qs, float (&sdq)[kRowBlock][2]) {
   const int r0 = blockIdx.x * kRowBlock, r = r0 + threadIdx.x;
-  if (p.th.h) {
-    row_heads(p.th, 2, p.B, r0, hs);
+  if (p.th.h && p.qh.h && p.th.H == p.qh.H && (p.th.H & 15) == 0 && p.th.H <= 256) {
+    row_heads2(p.th, p.qh, 2, p.B, r0, hs, qs);   // both heads, loads issued together
     __syncthreads();
+  } else {
+    if (p.th.h) {
+      row_heads(p.th, 2, p.B, r0, hs);
+      __syncthreads();
+    }
+    if (p.qh.h) {   // the critic's own last layer on (obs, a)
+      row_heads(p.qh, 2, p.B, r0, qs);
+      __syncthreads();
+    }
   }
   if (threadIdx.x >= kRowBlock || r >= p.B) return;
   const float* tq = p.th.h ? &hs.out[threadIdx.x][0] : p.tq + 2L * r;
-  const float q0 = p.q[2L * r], sd = expf(p.q[2L * r + 1]);
+  const float* qv = p.qh.h ? &qs.out[threadIdx.x][0] : p.q + 2L * r;
+  const float q0 = qv[0], sd = expf(qv[1]);
   const float t0 = tq[0], tsd = expf(tq[1]);
   const float rew = p.batch[(long)r * p.ld_batch + p.off_rew];
   const float term = p.batch[(long)r * p.ld_batch + p.off_term];
@@ -772,12 +782,40 @@ __global__ void __launch_bounds__(256) gauss_targets_kernel(GaussTargetArgs p) {
   const float yq = __fadd_rn(__fmul_rn(p.reward_scale, rew), __fmul_rn(gd, t0));
   const float invB = 1.f / (float)p.B;
   const float d0 = q0 - yq, d1 = sd - ys;
-  p.dq[2L * r] = __fmul_rn(2.f * d0, invB);
-  p.dq[2L * r + 1] = __fmul_rn(__fmul_rn(2.f * d1, invB), sd);
+  const float g0 = __fmul_rn(2.f * d0, invB), g1 = __fmul_rn(__fmul_rn(2.f * d1, invB), sd);
+  p.dq[2L * r] = g0;
+  p.dq[2L * r + 1] = g1;
+  sdq[threadIdx.x][0] = g0;
+  sdq[threadIdx.x][1] = g1;
   p.y[2L * r] = yq;
   p.y[2L * r + 1] = ys;
   p.sqe[2L * r] = d0 * d0;
   p.sqe[2L * r + 1] = d1 * d1;
+}
+
+// the row logic, then (p.dh2) the 16 rows' backward into the last hidden
+// layer by the whole block, as particle_targets_kernel's
+__global__ void __launch_bounds__(256) gauss_targets_kernel(GaussTargetArgs p) {
+  __shared__ RowHeadLds hs, qs;
+  __shared__ float sdq[kRowBlock][2];
+  gauss_targets_rows(p, hs, qs, sdq);
+  if (!p.dh2) return;
+  __syncthreads();
+  const int r0 = blockIdx.x * kRowBlock, H = p.qh.H, n4 = H >> 2;
+  for (int e = threadIdx.x; e < kRowBlock * n4; e += 256) {
+    const int rr = e / n4, c = 4 * (e - rr * n4), m = r0 + rr;
+    if (m >= p.B) continue;
+    const float4 h = *reinterpret_cast<const float4*>(p.qh.h + (long)m * H + c);
+    const float4 w0 = *reinterpret_cast<const float4*>(p.qh.w + c);
+    const float4 w1 = *reinterpret_cast<const float4*>(p.qh.w + H + c);
+    const float g0 = sdq[rr][0], g1 = sdq[rr][1];
+    float4 o;   // k order, as the GEMM's accumulation
+    o.x = h.x > 0.f ? fmaf(g1, w1.x, g0 * w0.x) : 0.f;
+    o.y = h.y > 0.f ? fmaf(g1, w1.y, g0 * w0.y) : 0.f;
+    o.z = h.z > 0.f ? fmaf(g1, w1.z, g0 * w0.z) : 0.f;
+    o.w = h.w > 0.f ? fmaf(g1, w1.w, g0 * w0.w) : 0.f;
+    *reinterpret_cast<float4*>(p.dh2 + (long)m * H + c) = o;
+  }
 }
 
 // Policy-loss seeds through the post-step critic (gaussian_trainer.py:323-336,
@@ -843,6 +881,102 @@ __global__ void __launch_bounds__(256) det_head_backward_kernel(DetHeadBwdArgs p
   float* dh = p.dhead[g] + (long)r * 2 * Da;
   dh[j] = __fmul_rn(p.da[g][idx], __fsub_rn(1.f, __fmul_rn(a, a)));
   dh[Da + j] = 0.f;
+}
+
+// One-hidden-layer critics: seed, last-layer dX, action-column dX and the
+// deterministic head's backward for both policy losses (DetSeedHeadBwdArgs).
+// 16 rows per 256-thread block, blockIdx.y = segment; 16 lanes per row.
+// dh1 goes through LDS in chunks of kDshChunk hidden units: lane l of a row
+// computes units l, l + 16, ... (coalesced rows of h1n and W_last); then lane
+// (phase, j) sums every nph-th unit of the chunk times its action column j --
+// the lanes of a row read whole rows of W0[:, Do:], contiguous in j, and the
+// four rows of a wave read the same addresses -- and the phases are added by
+// a fixed butterfly inside the row's 16 lanes.  No thread leaves early: rows
+// past B are clamped and only their stores are skipped.
+constexpr int kDshChunk = 256;
+__global__ void __launch_bounds__(256) det_seed_head_backward_kernel(DetSeedHeadBwdArgs p) {
+  __shared__ RowHeadLds hs;
+  __shared__ float sg[kRowBlock][kMaxHeads];
+  __shared__ float sdh[kRowBlock][kDshChunk + 1];
+  const int seg = blockIdx.y;
+  const int r0 = blockIdx.x * kRowBlock;
+  const int K = p.K, H = p.hn.H, Da = p.Da, B = p.B;
+  const float g0 = -(1.f / (float)B);
+  if (seg == 0) {
+    row_heads(p.hn, K, B, r0, hs);   // (-> QN1)
+    __syncthreads();
+    if (threadIdx.x < kRowBlock) {
+      const int t = threadIdx.x;
+      if (p.gauss) {   // gauss_seed_kernel
+        const float sd = expf(hs.out[t][1]);
+        if (r0 + t < B) p.ub[r0 + t] = __fadd_rn(hs.out[t][0], __fmul_rn(p.std_bound, sd));
+        sg[t][0] = g0;
+        sg[t][1] = __fmul_rn(__fmul_rn(g0, p.std_bound), sd);
+      } else {         // particle_ub_seed_kernel
+        float v[kMaxHeads];
+        int ix[kMaxHeads];
+        load_row16(&hs.out[t][0], K, v, ix);
+        sort16(v, ix);
+        int sel = ix[0];
+        float ub = v[0];
+#pragma unroll
+        for (int i = 1; i < kMaxHeads; ++i)
+          if (i == p.delta_index) { sel = ix[i]; ub = v[i]; }
+#pragma unroll
+        for (int i = 0; i < kMaxHeads; ++i) sg[t][i] = (i == sel) ? g0 : 0.f;
+        if (r0 + t < B) p.ub[r0 + t] = ub;
+      }
+    }
+  } else if (threadIdx.x < kRowBlock) {   // the target policy's constant seeds
+    const int t = threadIdx.x;
+#pragma unroll
+    for (int i = 0; i < kMaxHeads; ++i)
+      sg[t][i] = p.gauss ? (i == 0 ? g0 : 0.f) : g0 / (float)K;
+  }
+  __syncthreads();
+  const int row = threadIdx.x >> 4, l = threadIdx.x & 15;
+  const int m = min(r0 + row, B - 1);
+  const float* h1 = (seg == 0 ? p.hn.h : p.h1n1) + (long)m * H;
+  // lanes of a row over (phase, action dim): Dp = the power of two >= min(Da, 16)
+  int Dp = 1;
+  while (Dp < Da && Dp < 16) Dp <<= 1;
+  const int nph = 16 / Dp, jl = l & (Dp - 1), ph = l / Dp;
+  const int j0 = min(jl, Da - 1), j1 = min(jl + 16, Da - 1);   // (Da > 16: two dims per lane)
+  float acc0 = 0.f, acc1 = 0.f;
+  for (int c0 = 0; c0 < H; c0 += kDshChunk) {
+    const int nc = min(kDshChunk, H - c0);
+    for (int i = l; i < nc; i += 16) {
+      const int n = c0 + i;
+      float a = 0.f;
+      for (int k = 0; k < K; ++k) a = fmaf(sg[row][k], p.hn.w[(long)k * H + n], a);
+      sdh[row][i] = h1[n] > 0.f ? a : 0.f;
+    }
+    __syncthreads();
+    for (int i = ph; i < nc; i += nph) {
+      const float d = sdh[row][i];
+      const float* w = p.wa + (long)(c0 + i) * p.ld_wa;
+      acc0 = fmaf(d, w[j0], acc0);
+      acc1 = fmaf(d, w[j1], acc1);
+    }
+    __syncthreads();
+  }
+  for (int off = Dp; off < 16; off <<= 1) {
+    acc0 += __shfl_xor(acc0, off, 64);
+    acc1 += __shfl_xor(acc1, off, 64);
+  }
+  if (r0 + row >= B || ph != 0) return;
+  const float* act = p.act[seg] + (long)m * Da;
+  float* dh = p.dhead[seg] + (long)m * 2 * Da;
+  if (jl < Da) {
+    const float a = act[jl];
+    dh[jl] = __fmul_rn(acc0, __fsub_rn(1.f, __fmul_rn(a, a)));   // policies.py:286-288
+    dh[Da + jl] = 0.f;
+  }
+  if (jl + 16 < Da) {
+    const float a = act[jl + 16];
+    dh[jl + 16] = __fmul_rn(acc1, __fsub_rn(1.f, __fmul_rn(a, a)));
+    dh[Da + jl + 16] = 0.f;
+  }
 }
 
 // --------------------------------------------------------------------------
@@ -940,7 +1074,8 @@ hipError_t launch_ddpg_head_backward(const DdpgHeadBwdArgs& a, hipStream_t s) {
 }
 
 hipError_t launch_gauss_targets(const GaussTargetArgs& a, hipStream_t s) {
-  if (!head_ok(a.th)) return hipErrorInvalidValue;
+  if (!head_ok(a.th) || !head_ok(a.qh)) return hipErrorInvalidValue;
+  if (a.dh2 && (!a.qh.h || (a.qh.H & 3))) return hipErrorInvalidValue;
   OAC_LAUNCH(gauss_targets_kernel, dim3((a.B + kRowBlock - 1) / kRowBlock), dim3(256), 0, s, a);
   return hipGetLastError();
 }
@@ -952,6 +1087,17 @@ hipError_t launch_gauss_seed(const GaussSeedArgs& a, hipStream_t s) {
 hipError_t launch_particle_ub_seed(const ParticleUbSeedArgs& a, hipStream_t s) {
   if (a.K > kMaxHeads || !head_ok(a.hn)) return hipErrorInvalidValue;
   OAC_LAUNCH(particle_ub_seed_kernel, dim3((a.B + kRowBlock - 1) / kRowBlock), dim3(256), 0, s, a);
+  return hipGetLastError();
+}
+hipError_t launch_det_seed_head_backward(const DetSeedHeadBwdArgs& a, hipStream_t s) {
+  if (!a.hn.h || !head_ok(a.hn) || !a.h1n1 || !a.wa || !a.ub || a.B < 1 || a.K < 1 ||
+      a.K > kMaxHeads || (a.gauss && a.K != 2) || a.Da < 1 || a.Da > 32 ||
+      a.delta_index < 0 || a.delta_index >= kMaxHeads)
+    return hipErrorInvalidValue;
+  for (int g = 0; g < 2; ++g)
+    if (!a.act[g] || !a.dhead[g]) return hipErrorInvalidValue;
+  OAC_LAUNCH(det_seed_head_backward_kernel, dim3((a.B + kRowBlock - 1) / kRowBlock, 2), dim3(256),
+             0, s, a);
   return hipGetLastError();
 }
 hipError_t launch_det_head_backward(const DetHeadBwdArgs& a, hipStream_t s) {

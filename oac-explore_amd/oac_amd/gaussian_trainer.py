@@ -1,7 +1,9 @@
 """Drop-in ``GaussianTrainer`` of the g-oac recipes
 (/root/reference/trainer/gaussian_trainer.py:14-538, the trainer main.py
 builds for ``--alg g-oac``, main.py:219-233), in the configuration every
-reproduce_g-oac*.sh recipe runs: ``--share_layers`` (one critic with two
+reproduce_g-oac*.sh recipe runs -- networks of two hidden layers (the Humanoid
+recipes) or of one (main.py's ``--num_layers 1`` default: the riverswim
+recipes; width a multiple of 4) -- ``--share_layers`` (one critic with two
 outputs, Q mean | log std, exp'd by ``positive=[False, True]``), the
 deterministic policy (GaussianTrainer's default, not overridden for g-oac),
 optionally ``--counts`` / ``std_soft_update`` / ``--mean_update``.  The step

@@ -116,11 +116,13 @@ class ArenaFlattenMlp(nn.Module):
         self.input_size, self.output_size = din, out_dim
         self.fc0 = _ArenaLinear(_view(arena, base + L.q_fc0_w, hidden, din),
                                 _view(arena, base + L.q_fc0_b, hidden))
-        self.fc1 = _ArenaLinear(_view(arena, base + L.q_fc1_w, hidden, hidden),
-                                _view(arena, base + L.q_fc1_b, hidden))
+        self.fcs = [self.fc0]
+        if L.q_fc1_w >= 0:   # (-1: a one-hidden-layer critic, no fc1 in the arena)
+            self.fc1 = _ArenaLinear(_view(arena, base + L.q_fc1_w, hidden, hidden),
+                                    _view(arena, base + L.q_fc1_b, hidden))
+            self.fcs.append(self.fc1)
         self.last_fc = _ArenaLinear(_view(arena, base + L.q_last_w, out_dim, hidden),
                                     _view(arena, base + L.q_last_b, out_dim))
-        self.fcs = [self.fc0, self.fc1]
         self.arena, self.base = arena, base
         self.hidden, self.obs_dim, self.act_dim = hidden, obs_dim, act_dim
         self._offs = _offsets(L.q_fc0_w, L.q_fc0_b, L.q_fc1_w, L.q_fc1_b, L.q_last_w, L.q_last_b)
@@ -157,12 +159,14 @@ class ArenaTanhGaussianPolicy(nn.Module):
         hb = _view(arena, base + L.pol_head_b, 2 * Da)
         self.fc0 = _ArenaLinear(_view(arena, base + L.pol_fc0_w, hidden, obs_dim),
                                 _view(arena, base + L.pol_fc0_b, hidden))
-        self.fc1 = _ArenaLinear(_view(arena, base + L.pol_fc1_w, hidden, hidden),
-                                _view(arena, base + L.pol_fc1_b, hidden))
+        self.fcs = [self.fc0]
+        if L.pol_fc1_w >= 0:   # (-1: a one-hidden-layer policy)
+            self.fc1 = _ArenaLinear(_view(arena, base + L.pol_fc1_w, hidden, hidden),
+                                    _view(arena, base + L.pol_fc1_b, hidden))
+            self.fcs.append(self.fc1)
         self.last_fc = _ArenaLinear(hw[:Da], hb[:Da])
         if std is None:
             self.last_fc_log_std = _ArenaLinear(hw[Da:], hb[Da:])
-        self.fcs = [self.fc0, self.fc1]
         self.obs_dim, self.action_dim = obs_dim, act_dim
         self.input_size, self.output_size = obs_dim, act_dim
         self.std = self.log_std = None

@@ -1,7 +1,9 @@
 """Drop-in ``ParticleTrainer`` of /root/reference/trainer/particle_trainer.py
 (12-525): the trainer main.py builds for ``--alg p-oac`` without
 ``--beta_UB`` (main.py:198-204, 364, 488-490) -- i.e. every reproduce_p-oac*.sh
-recipe -- with the shared-layer K-particle critic (``--share_layers``), the
+recipe, at two hidden layers (the Humanoid recipes) or one (main.py's
+``--num_layers 1`` default: the riverswim recipes; width a multiple of 4) --
+with the shared-layer K-particle critic (``--share_layers``), the
 deterministic policy (``deterministic = not --stochastic``), and optionally
 ``--counts`` / ``std_soft_update`` / ``--mean_update`` /
 ``rescale_targets_around_mean``.  Per step: sorted-particle TD targets with

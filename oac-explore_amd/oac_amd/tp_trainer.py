@@ -37,7 +37,9 @@ class _TargetPolicyTrainer(_ArenaTrainer):
         """Arena modules initialised from the producers' state_dicts, and the
         reference's optimizer views (policy, target_policy, shared critic)."""
         pol_sd = {k: v.detach() for k, v in ref_pol.state_dict().items()}
-        Do, Da, H, K = _dims_from_state(pol_sd, ref_q.state_dict())
+        Do, Da, H, K, self.n_hidden = _dims_from_state(pol_sd, ref_q.state_dict(), depths=(1, 2))
+        if self.n_hidden == 1 and H % 4:
+            raise ValueError(f"one hidden layer: the width must be a multiple of 4, got {H}")
         if K != self._q_out:
             raise ValueError(f"share_layers: q_producer must build a critic with {self._q_out} "
                              f"outputs, got {K}")

@@ -43,19 +43,30 @@ def row_layout(obs_dim, act_dim):
                 off_term=off_term, off_next_obs=off_next)
 
 
-def _dims_from_state(pol_sd, q_sd, fixed_std=False):
-    for sd in (pol_sd, q_sd):
-        n_hidden = sum(1 for k in sd if k.startswith("fc") and k.endswith(".weight"))
-        if n_hidden != 2:
-            raise ValueError(f"liboac_amd implements the 2-hidden-layer MLPs of the reference "
-                             f"recipes (layer_size x 2); got {n_hidden} hidden layers")
+def _depth(sd):
+    return sum(1 for k in sd if k.startswith("fc") and k.endswith(".weight"))
+
+
+def _dims_from_state(pol_sd, q_sd, fixed_std=False, depths=(2,)):
+    """(Do, Da, H, Q) of the producers' networks -- and the depth as a fifth
+    value when the caller takes more than the two-layer MLPs (``depths``)."""
+    dp, dq = _depth(pol_sd), _depth(q_sd)
+    if dp != dq:
+        raise ValueError(f"policy and critic must have the same depth; got {dp} and {dq} "
+                         f"hidden layers")
+    if dp not in depths:
+        raise ValueError(f"liboac_amd implements the 2-hidden-layer MLPs of the reference "
+                         f"recipes (layer_size x 2), and 1-hidden-layer MLPs (--num_layers 1) "
+                         f"for GaussianTrainer and ParticleTrainer only; got {dp} hidden layers")
     H, Do = pol_sd["fc0.weight"].shape
     Da = pol_sd["last_fc.weight"].shape[0]
-    if q_sd["fc0.weight"].shape != (H, Do + Da) or pol_sd["fc1.weight"].shape != (H, H):
+    if q_sd["fc0.weight"].shape != (H, Do + Da) or \
+            (dp == 2 and pol_sd["fc1.weight"].shape != (H, H)):
         raise ValueError("policy / critic shapes are inconsistent")
     if "last_fc_log_std.weight" not in pol_sd and not fixed_std:   # (fixed std: DDPGTrainer only)
         raise ValueError("only the learned-std TanhGaussianPolicy (std=None) is supported")
-    return Do, Da, H, q_sd["last_fc.weight"].shape[0]
+    dims = Do, Da, H, q_sd["last_fc.weight"].shape[0]
+    return dims + (dp,) if len(depths) > 1 else dims
 
 
 def _twin_views(arena, other, params):
@@ -138,6 +149,7 @@ class _ArenaTrainer(object):
 
     _kind = _lib.OAC_KIND_SAC
     _q_out = 1
+    n_hidden = 2   # hidden layers of the policy and the critic (1: the det trainers only)
 
     def _alloc(self, Do, Da, H, device):
         L = _lib.lib()
@@ -194,6 +206,7 @@ class _ArenaTrainer(object):
         c.seed = self.seed
         c.gemm_cfg = self._gemm_cfg
         c.world_size = 1
+        c.n_hidden = self.n_hidden
         return c
 
     def _plan(self, B, replay=None, idx=None, ring_slots=0, count_state=None):
