@@ -98,6 +98,12 @@ typedef struct oac_sac_config {
    * default, the riverswim recipes).  At 1 the layout has no fc1 tensors:
    * pol_fc1_* and q_fc1_* are -1; hidden must then be a multiple of 4 */
   int n_hidden;
+  /* OAC_KIND_GAUSS / OAC_KIND_PARTICLE_UB, world_size == 1: --global_opt
+   * (gaussian_trainer.py:337-341, particle_trainer.py:343-346).  The step leaves
+   * the policy block of params / adam_m / adam_v untouched (it trains the critic
+   * and the target_policy only); the policy is trained by the sweep,
+   * oac_sac_policy_opt_* below.  0 in a zero-initialised config */
+  int global_opt;
 } oac_sac_config;
 
 /* Flat parameter arena layout (float offsets; every tensor 16-byte aligned).
@@ -238,6 +244,38 @@ int oac_sac_set_step_graph(oac_sac* h, void* graph_exec, int flags);
  * phase 5 = the rest of phase 1, so 0, [alpha all-reduce || 4], 5, 2, 3 is
  * the same step with the first exchange overlapped. */
 int oac_sac_step_phase(oac_sac* h, int phase, int flags, void* stream);
+
+/* ------------------------------------------------- global_opt policy sweep */
+/* trainer.optimize_policies -> utils/core.py:64-137 optimize_policy, on a
+ * handle created with global_opt = 1, batch = N (the rows of one iteration:
+ * the whole dataset) and replay = rows of the step's row layout whose obs
+ * columns hold the dataset.  Everything is stream-ordered with no host
+ * synchronisation inside a call.  A global_opt handle rejects
+ * OAC_STEP_USE_GRAPH, oac_sac_step_phase and oac_sac_set_allreduce.
+ *
+ * reset: params' policy block = init_policy[0 : pol_size] (device, policy-
+ * shaped; core.py:68).  The Adam moments and the sweep's counters stay.
+ *
+ * iter: one gradient step of the policy on N rows (core.py:80-98): policy
+ * forward, a = tanh(mean), the current critic on (obs, a), the upper bound's
+ * seed scaled -1/N, critic dX to dL/da, head backward, policy dW, and the
+ * policy-only Adam with t = the sweep's own count + 1 (no Polyak; critic and
+ * target_policy untouched; step_state untouched).
+ *   idx      host int64 [N] row indices into replay, staged through the
+ *            handle's host ring (oac_sac_set_host_ring; slot bc % ring_slots,
+ *            bc = a counter the caller advances by one per staged iteration)
+ *            and gathered obs-only on the device; NULL: rows 0..N-1 of replay
+ *            read in place, no gather launch (needs replay_rows > N: the
+ *            products' k-contiguous loads may read past a row's obs columns)
+ *   opt_state  caller-owned 64 zeroed device bytes: int64 iteration count at
+ *            offset 0 (policy_optimizer's `step`), then the published bias
+ *            corrections of the iteration (the layout of step_state)
+ *   history_row  device float[2]: {-mean(upper bound), ||policy grad||_2} of
+ *            this iteration, both summed in a fixed order (deterministic)
+ * After a call grads' policy block holds the iteration's gradient. */
+int oac_sac_policy_opt_reset(oac_sac* h, const float* init_policy, void* stream);
+int oac_sac_policy_opt_iter(oac_sac* h, const int64_t* idx, int64_t bc, void* opt_state,
+                            float* history_row, void* stream);
 
 /* ------------------------------------------------ data-parallel exchanges */
 /* The data-parallel step with its exchanges issued by the library itself

@@ -9,6 +9,8 @@
 // float4 pass over g, p, m, v (and target).  Data-parallel: a reduce-only pass
 // writes the summed gradient, the caller all-reduces it, then the update pass
 // runs with gscale = 1/world.
+#include <algorithm>
+
 #include "oac_common.h"
 #include "kernels.h"
 #include "adam_common.h"
@@ -72,5 +74,75 @@ hipError_t launch_adam(const AdamArgs& a, hipStream_t s) {
   return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------
+// global_opt sweep (utils/core.py:64-137): the policy-only Adam of one
+// iteration and the iteration's history row (PolicyOptAdamArgs).
+// ---------------------------------------------------------------------------
+// Sum of (x, y) over the workgroup in a fixed order: the wave's butterfly,
+// then the four wave sums in wave order.  The result is valid in thread 0.
+__device__ __forceinline__ void block_sum2(float& x, float& y, float (&sh)[2][4]) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    x += __shfl_xor(x, off, 64);
+    y += __shfl_xor(y, off, 64);
+  }
+  __syncthreads();   // (sh may still be read from an earlier call)
+  if ((threadIdx.x & 63) == 0) { sh[0][threadIdx.x >> 6] = x; sh[1][threadIdx.x >> 6] = y; }
+  __syncthreads();
+  x = ((sh[0][0] + sh[0][1]) + sh[0][2]) + sh[0][3];
+  y = ((sh[1][0] + sh[1][1]) + sh[1][2]) + sh[1][3];
+}
+
+__global__ void __launch_bounds__(256) policy_opt_adam_kernel(PolicyOptAdamArgs q) {
+  __shared__ float sh[2][4];
+  __shared__ int s_last;
+  const AdamArgs& a = q.a;
+  // t = n_steps + 1 of the sweep's own counters (bias corrections published by
+  // the iteration's first launch); n_steps is advanced by the last workgroup
+  // to arrive, after every workgroup has read it
+  const AdamConsts c = adam_consts(a.state, 0, a.lr, a.beta1, a.beta2, a.eps, nullptr, 0.f, 1);
+  const long n4 = a.n >> 2;
+  const long stride = (long)gridDim.x * 256;
+  float ss = 0.f, ub = 0.f;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride) {
+    const float4 g = adam_flat_elem(c, a, i);
+    ss += ((g.x * g.x + g.y * g.y) + g.z * g.z) + g.w * g.w;
+  }
+  for (long r = (long)blockIdx.x * 256 + threadIdx.x; r < q.N; r += stride) ub += q.ub[r];
+  block_sum2(ss, ub, sh);
+  if (threadIdx.x == 0) {
+    // the partials and the ticket by one thread: its release orders them
+    q.part[2 * blockIdx.x] = ss;
+    q.part[2 * blockIdx.x + 1] = ub;
+    const unsigned t = __hip_atomic_fetch_add(q.ticket, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+    s_last = t == gridDim.x - 1;
+  }
+  __syncthreads();
+  if (!s_last) return;
+  ss = 0.f; ub = 0.f;
+  for (int b = threadIdx.x; b < (int)gridDim.x; b += 256) {   // workgroup order per thread
+    ss += __hip_atomic_load(q.part + 2 * b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    ub += __hip_atomic_load(q.part + 2 * b + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  block_sum2(ss, ub, sh);
+  if (threadIdx.x != 0) return;
+  q.hist[0] = -(ub / (float)q.N);
+  q.hist[1] = __fsqrt_rn(ss);
+  a.state->n_steps += 1;
+  __hip_atomic_store(q.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+hipError_t launch_policy_opt_adam(const PolicyOptAdamArgs& q, hipStream_t s) {
+  const AdamArgs& a = q.a;
+  if ((a.n & 3) || a.n < 4 || !a.state || !q.ub || q.N < 1 || !q.part || !q.ticket || !q.hist ||
+      a.reduce_only || a.target)
+    return hipErrorInvalidValue;
+  // workgroups: one per 256 float4 of the block, and enough for the [N] column
+  const long rows = (q.N + 1023) / 1024;
+  int blocks = std::max(adam_blocks(a.n >> 2, 256), (int)std::min(rows, 256L));
+  blocks = std::min(blocks, kPolicyOptMaxBlocks);
+  OAC_LAUNCH(policy_opt_adam_kernel, dim3(blocks), dim3(256), 0, s, q);
+  return hipGetLastError();
+}
 
 }  // namespace oac

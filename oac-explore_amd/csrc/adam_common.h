@@ -149,7 +149,8 @@ __device__ __forceinline__ void adam_flat_finish(const AdamConsts& c, const Adam
 }
 
 // float4 i of a flat range, one thread (slab order: slab_chunk)
-__device__ __forceinline__ void adam_flat_elem(const AdamConsts& c, const AdamArgs& a, long i) {
+// (returns the float4's reduced gradient)
+__device__ __forceinline__ float4 adam_flat_elem(const AdamConsts& c, const AdamArgs& a, long i) {
   if (a.S > 1 || a.gslab != a.g) {
     const int S = slab_count(a, i);
     float4 g = slab_chunk(a, i, 0, S);
@@ -157,9 +158,11 @@ __device__ __forceinline__ void adam_flat_elem(const AdamConsts& c, const AdamAr
 #pragma unroll 1
     for (int ch = 1; ch < nc; ++ch) add4(g, slab_chunk(a, i, ch, S));
     adam_flat_finish(c, a, i, g, true);
-  } else {
-    adam_flat_finish(c, a, i, reinterpret_cast<const float4*>(a.g)[i], false);
+    return g;
   }
+  const float4 g = reinterpret_cast<const float4*>(a.g)[i];
+  adam_flat_finish(c, a, i, g, false);
+  return g;
 }
 
 // side workgroup `blk` of `nblk` (256 threads each): the flat ranges of

@@ -61,6 +61,7 @@ enum GWs {
   G_DQ, G_DH2Q, G_DH1Q,
   G_PN, G_H1N, G_H2N, G_PN3, G_H1N3, G_H2N3, G_GQ, G_GQ3, G_DH2N, G_DH1N, G_DH2N3, G_DH1N3,
   G_DA, G_DA3, G_DHEAD, G_DHEAD3, G_DH2P, G_DH1P, G_DH2TP, G_DH1TP,
+  G_OPT,   // global_opt sweep: per-workgroup partials of the history row, then the ticket word
   G_COUNT
 };
 static_assert(G_COUNT <= WS_GSLAB_Q, "workspace ids");
@@ -83,6 +84,7 @@ void det_layout_workspace(SacPlan& p) {
     set(id, B, H);
   for (int id : {G_DA, G_DA3}) set(id, B, Da);
   for (int id : {G_DHEAD, G_DHEAD3}) set(id, B, 2 * Da);
+  if (c.global_opt) set(G_OPT, 1, 2 * kPolicyOptMaxBlocks + 64);
   finish_layout(p);
 }
 
@@ -107,10 +109,11 @@ static int dphase0(SacPlan& p, int flags, hipStream_t s) {
   const float* npol = c.mean_update ? tpol : (p.b.next_policy ? p.b.next_policy : pol);
   const float* q = p.b.params + L.q1_base;
   const float* tq = p.b.targets;
+  const bool go = p.c.global_opt != 0;
   {
     GemmBatch gb{};
     publish_step(p, gb);
-    add(gb, pol_l0(p, pol, obs, G_H1P));
+    if (!go) add(gb, pol_l0(p, pol, obs, G_H1P));   // (global_opt: no policy loss in the step)
     add(gb, pol_l0(p, npol, nobs, G_H1P2));
     add(gb, pol_l0(p, tpol, obs, G_H1TP));
     add(gb, critic_l0_rank(p, q, obs, X + c.off_act, RS, G_P, G_H1Q));
@@ -120,7 +123,7 @@ static int dphase0(SacPlan& p, int flags, hipStream_t s) {
   const bool sh = shallow(p);
   if (!sh) {
     GemmBatch gb{};
-    add(gb, pol_l1(p, pol, G_H1P, G_H2P));
+    if (!go) add(gb, pol_l1(p, pol, G_H1P, G_H2P));
     add(gb, pol_l1(p, npol, G_H1P2, G_H2P2));
     add(gb, pol_l1(p, tpol, G_H1TP, G_H2TP));
     add(gb, critic_l1(p, q, G_H1Q, G_H2Q));
@@ -133,17 +136,19 @@ static int dphase0(SacPlan& p, int flags, hipStream_t s) {
     a.ld_wa = Dq; a.det = 1;
     a.B = B; a.H = H; a.Da = Da;
     a.col_chunks = std::max(1, (H + (B >= 1024 ? 127 : 63)) / (B >= 1024 ? 128 : 64));
-    HeadSeg& s0 = a.seg[0];   // policy(obs) -> a~ (post-step critic, phase 2)
+    // (global_opt: the policy(obs) segment is not run; the other two move up)
+    const int k0 = go ? 2 : 0, k1 = go ? 0 : 1, k2 = go ? 1 : 2;
+    HeadSeg& s0 = a.seg[k0];   // policy(obs) -> a~ (post-step critic, phase 2)
     s0.h2 = p.W(sh ? G_H1P : G_H2P); s0.wh = pol + L.pol_head_w; s0.bh = pol + L.pol_head_b;
     s0.head = p.W(OAC_WS_HEAD1); s0.act = p.W(OAC_WS_ACT1);
-    HeadSeg& s1 = a.seg[1];   // next-action policy(next_obs) -> QT(next_obs, a')
+    HeadSeg& s1 = a.seg[k1];   // next-action policy(next_obs) -> QT(next_obs, a')
     s1.h2 = p.W(sh ? G_H1P2 : G_H2P2); s1.wh = npol + L.pol_head_w; s1.bh = npol + L.pol_head_b;
     s1.head = p.W(OAC_WS_HEAD2); s1.act = p.W(OAC_WS_ACT2);
     s1.n_nets = 1; s1.wa[0] = tq + L.q_fc0_w + Do; s1.pre[0] = p.W(G_PT); s1.h1[0] = p.W(G_H1T);
-    HeadSeg& s2 = a.seg[2];   // target_policy(obs) -> a~_T (phase 2)
+    HeadSeg& s2 = a.seg[k2];   // target_policy(obs) -> a~_T (phase 2)
     s2.h2 = p.W(sh ? G_H1TP : G_H2TP); s2.wh = tpol + L.pol_head_w; s2.bh = tpol + L.pol_head_b;
     s2.head = p.W(OAC_WS_HEAD3); s2.act = p.W(OAC_WS_ACT3);
-    RUN_ROW(p, s, launch_policy_head(a, 3, s));
+    RUN_ROW(p, s, launch_policy_head(a, go ? 2 : 3, s));
   }
   return 0;
 }
@@ -242,9 +247,11 @@ static int dphase2(SacPlan& p, hipStream_t s, bool fused) {
   const int B = c.batch, H = c.hidden, Da = c.act_dim, K = c.q_out;
   float* X = p.W(OAC_WS_BATCH);
   const float* q = p.b.params + L.q1_base;
+  // global_opt: the target policy's loss only, and its block's Adam
+  const bool go = c.global_opt != 0;
   {
     GemmBatch gb{};
-    add(gb, critic_l0_rank(p, q, X + c.off_obs, p.W(OAC_WS_ACT1), Da, G_PN, G_H1N));
+    if (!go) add(gb, critic_l0_rank(p, q, X + c.off_obs, p.W(OAC_WS_ACT1), Da, G_PN, G_H1N));
     add(gb, critic_l0_rank(p, q, X + c.off_obs, p.W(OAC_WS_ACT3), Da, G_PN3, G_H1N3));
     if (run_gemm(p, gb, s)) return 1;
   }
@@ -261,29 +268,31 @@ static int dphase2(SacPlan& p, hipStream_t s, bool fused) {
       a.ub = p.W(OAC_WS_QNEW);
       a.gauss = c.kind == OAC_KIND_GAUSS; a.std_bound = c.std_bound; a.delta_index = c.delta_index;
       a.B = B; a.K = K; a.Da = Da;
+      a.seg_lo = go ? 1 : 0; a.nseg = go ? 1 : 2;
       RUN_ROW(p, s, launch_det_seed_head_backward(a, s));
     }
     {
       GemmBatch gb{};
-      add(gb, pol_head_dw(p, 0, G_DHEAD, G_H1P));
-      add(gb, pol_head_dx(p, 0, G_DHEAD, G_DH1P, G_H1P));
+      if (!go) add(gb, pol_head_dw(p, 0, G_DHEAD, G_H1P));
+      if (!go) add(gb, pol_head_dx(p, 0, G_DHEAD, G_DH1P, G_H1P));
       add(gb, pol_head_dw(p, tp, G_DHEAD3, G_H1TP));
       add(gb, pol_head_dx(p, tp, G_DHEAD3, G_DH1TP, G_H1TP));
       if (run_gemm(p, gb, s)) return 1;
     }
     GemmBatch gb{};
-    add(gb, pol_l0_dw(p, 0, G_DH1P));
+    if (!go) add(gb, pol_l0_dw(p, 0, G_DH1P));
     add(gb, pol_l0_dw(p, tp, G_DH1TP));
     if (fused) {   // [policy | target_policy] Adam in the epilogue; tail blocks: the heads
       const long off[2] = {(long)L.pol_head_w, (long)(L.tpol_base + L.pol_head_w)};
       const long n[2] = {(long)(L.pol_size - L.pol_head_w), (long)(L.pol_size - L.pol_head_w)};
-      fuse_adam(gb, policy_adam(p, 0, nullptr), 2, off, n);
+      if (go) fuse_adam(gb, tpol_adam(p), 1, off, n);   // (offsets from the block's base)
+      else fuse_adam(gb, policy_adam(p, 0, nullptr), 2, off, n);
     }
     return run_gemm(p, gb, s);
   }
   {
     GemmBatch gb{};
-    add(gb, critic_l1(p, q, G_H1N, G_H2N));
+    if (!go) add(gb, critic_l1(p, q, G_H1N, G_H2N));
     add(gb, critic_l1(p, q, G_H1N3, G_H2N3));
     if (run_gemm(p, gb, s)) return 1;
   }
@@ -297,6 +306,7 @@ static int dphase2(SacPlan& p, hipStream_t s, bool fused) {
     std::memset(&a, 0, sizeof(a));
     a.qn = p.W(OAC_WS_QN1); a.qt = p.W(OAC_WS_QN2); a.hn = hn; a.std_bound = c.std_bound; a.B = B;
     a.g = p.W(G_GQ); a.gt = p.W(G_GQ3); a.ub = p.W(OAC_WS_QNEW);
+    a.segs = go ? 2 : 3;
     RUN_ROW(p, s, launch_gauss_seed(a, s));
   } else {
     ParticleUbSeedArgs a;
@@ -304,58 +314,61 @@ static int dphase2(SacPlan& p, hipStream_t s, bool fused) {
     a.qn = p.W(OAC_WS_QN1); a.qt = p.W(OAC_WS_QN2); a.hn = hn; a.B = B; a.K = K;
     a.delta_index = c.delta_index;
     a.g = p.W(G_GQ); a.gt = p.W(G_GQ3); a.ub = p.W(OAC_WS_QNEW);
+    a.segs = go ? 2 : 3;
     RUN_ROW(p, s, launch_particle_ub_seed(a, s));
   }
   {
     GemmBatch gb{};
-    add(gb, critic_last_dx(p, G_GQ, G_DH2N, G_H2N));
+    if (!go) add(gb, critic_last_dx(p, G_GQ, G_DH2N, G_H2N));
     add(gb, critic_last_dx(p, G_GQ3, G_DH2N3, G_H2N3));
     if (run_gemm(p, gb, s)) return 1;
   }
   {
     GemmBatch gb{};
-    add(gb, critic_l1_dx(p, G_DH2N, G_DH1N, G_H1N));
+    if (!go) add(gb, critic_l1_dx(p, G_DH2N, G_DH1N, G_H1N));
     add(gb, critic_l1_dx(p, G_DH2N3, G_DH1N3, G_H1N3));
     if (run_gemm(p, gb, s)) return 1;
   }
   {
     GemmBatch gb{};
-    add(gb, critic_act_dx(p, q, G_DH1N, G_DA, Da));
+    if (!go) add(gb, critic_act_dx(p, q, G_DH1N, G_DA, Da));
     add(gb, critic_act_dx(p, q, G_DH1N3, G_DA3, Da));
     if (run_gemm(p, gb, s)) return 1;
   }
   {
     DetHeadBwdArgs a;
     std::memset(&a, 0, sizeof(a));
+    const int k3 = go ? 0 : 1;   // (global_opt: the target policy's segment alone)
     a.da[0] = p.W(G_DA); a.act[0] = p.W(OAC_WS_ACT1); a.dhead[0] = p.W(G_DHEAD);
-    a.da[1] = p.W(G_DA3); a.act[1] = p.W(OAC_WS_ACT3); a.dhead[1] = p.W(G_DHEAD3);
-    a.nseg = 2; a.B = B; a.act_dim = Da;
+    a.da[k3] = p.W(G_DA3); a.act[k3] = p.W(OAC_WS_ACT3); a.dhead[k3] = p.W(G_DHEAD3);
+    a.nseg = k3 + 1; a.B = B; a.act_dim = Da;
     RUN_ROW(p, s, launch_det_head_backward(a, s));
   }
   {
     GemmBatch gb{};
-    add(gb, pol_head_dw(p, 0, G_DHEAD, G_H2P));
-    add(gb, pol_head_dx(p, 0, G_DHEAD, G_DH2P, G_H2P));
+    if (!go) add(gb, pol_head_dw(p, 0, G_DHEAD, G_H2P));
+    if (!go) add(gb, pol_head_dx(p, 0, G_DHEAD, G_DH2P, G_H2P));
     add(gb, pol_head_dw(p, tp, G_DHEAD3, G_H2TP));
     add(gb, pol_head_dx(p, tp, G_DHEAD3, G_DH2TP, G_H2TP));
     if (run_gemm(p, gb, s)) return 1;
   }
   {
     GemmBatch gb{};
-    add(gb, pol_l1_dw(p, 0, G_DH2P, G_H1P));
-    add(gb, pol_l1_dx(p, 0, G_DH2P, G_DH1P, G_H1P));
+    if (!go) add(gb, pol_l1_dw(p, 0, G_DH2P, G_H1P));
+    if (!go) add(gb, pol_l1_dx(p, 0, G_DH2P, G_DH1P, G_H1P));
     add(gb, pol_l1_dw(p, tp, G_DH2TP, G_H1TP));
     add(gb, pol_l1_dx(p, tp, G_DH2TP, G_DH1TP, G_H1TP));
     if (run_gemm(p, gb, s)) return 1;
   }
   {
     GemmBatch gb{};
-    add(gb, pol_l0_dw(p, 0, G_DH1P));
+    if (!go) add(gb, pol_l0_dw(p, 0, G_DH1P));
     add(gb, pol_l0_dw(p, tp, G_DH1TP));
     if (fused) {   // [policy | target_policy] Adam in the epilogue; advances the step
       const long off[2] = {(long)L.pol_fc1_w, (long)(L.tpol_base + L.pol_fc1_w)};
       const long n[2] = {(long)(L.pol_size - L.pol_fc1_w), (long)(L.pol_size - L.pol_fc1_w)};
-      fuse_adam(gb, policy_adam(p, 0, nullptr), 2, off, n);
+      if (go) fuse_adam(gb, tpol_adam(p), 1, off, n);   // (offsets from the block's base)
+      else fuse_adam(gb, policy_adam(p, 0, nullptr), 2, off, n);
     }
     if (run_gemm(p, gb, s)) return 1;
   }
@@ -369,7 +382,158 @@ int det_run_step(SacPlan& p, int flags, hipStream_t s, int, int) {
   if (dphase1(p, flags, s, fused)) return 1;
   if (!fused && run_adam(p, critic_adam(p, 0, nullptr), s)) return 1;
   if (dphase2(p, s, fused)) return 1;
-  if (!fused && run_adam(p, policy_adam(p, 0, nullptr), s)) return 1;
+  if (!fused && run_adam(p, p.c.global_opt ? tpol_adam(p) : policy_adam(p, 0, nullptr), s)) return 1;
+  return 0;
+}
+
+// ----------------------------------------------------- global_opt sweep
+// One iteration of utils/core.py:64-137 optimize_policy: the policy's loss
+// -mean(upper bound of the CURRENT critic on (obs, tanh(mean_pi(obs)))) over
+// the plan's N = batch rows, its gradient and the policy-only Adam -- phase 2's
+// policy segment alone, on rows of its own, with counters of its own (opt).
+int det_policy_opt_iter(SacPlan& p, const int* rows, StepState* opt, float* hist, hipStream_t s) {
+  const oac_sac_config& c = p.c;
+  const oac_sac_layout& L = p.L;
+  const int B = c.batch, H = c.hidden, Do = c.obs_dim, Da = c.act_dim, K = c.q_out;
+  p.launches = 0;
+  p.slot = 0;
+  float* X = p.W(OAC_WS_BATCH);
+  if (rows) {   // the iteration's rows: their obs columns only
+    ObsGatherArgs g{p.b.replay, c.row_stride, rows, B, Do, c.off_obs, X};
+    TIMED(p, K_GATHER, s, OAC_HIP_CHECK(launch_obs_gather(g, s)));
+    p.launches++;
+  } else {
+    X = const_cast<float*>(p.b.replay);   // (read only)
+  }
+  struct Rows {   // pol_l0_dw reads the rows through p.X()
+    SacPlan& p;
+    ~Rows() { p.x_rows = nullptr; }
+  } guard{p};
+  p.x_rows = X;
+  const float* obs = X + c.off_obs;
+  const float* pol = p.b.params;
+  const float* q = p.b.params + L.q1_base;
+  const bool sh = shallow(p);
+  {
+    GemmBatch gb{};
+    gb.publish = opt; gb.pub_beta1 = c.beta1; gb.pub_beta2 = c.beta2;   // t = opt->n_steps + 1
+    add(gb, pol_l0(p, pol, obs, G_H1P));
+    if (run_gemm(p, gb, s)) return 1;
+  }
+  if (!sh) {
+    GemmBatch gb{};
+    add(gb, pol_l1(p, pol, G_H1P, G_H2P));
+    if (run_gemm(p, gb, s)) return 1;
+  }
+  {
+    HeadArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.ld_wa = Do + Da; a.det = 1;
+    a.B = B; a.H = H; a.Da = Da;
+    a.col_chunks = std::max(1, (H + (B >= 1024 ? 127 : 63)) / (B >= 1024 ? 128 : 64));
+    HeadSeg& s0 = a.seg[0];
+    s0.h2 = p.W(sh ? G_H1P : G_H2P); s0.wh = pol + L.pol_head_w; s0.bh = pol + L.pol_head_b;
+    s0.head = p.W(OAC_WS_HEAD1); s0.act = p.W(OAC_WS_ACT1);
+    RUN_ROW(p, s, launch_policy_head(a, 1, s));
+  }
+  {
+    GemmBatch gb{};
+    add(gb, critic_l0_rank(p, q, obs, p.W(OAC_WS_ACT1), Da, G_PN, G_H1N));
+    if (run_gemm(p, gb, s)) return 1;
+  }
+  if (sh) {
+    DetSeedHeadBwdArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.hn = RowHead{p.W(G_H1N), q + L.q_last_w, q + L.q_last_b, p.W(OAC_WS_QN1), H};
+    a.h1n1 = p.W(G_H1N3);   // (segment 1 is not run)
+    a.wa = q + L.q_fc0_w + Do; a.ld_wa = Do + Da;
+    a.act[0] = p.W(OAC_WS_ACT1); a.dhead[0] = p.W(G_DHEAD);
+    a.act[1] = p.W(OAC_WS_ACT3); a.dhead[1] = p.W(G_DHEAD3);
+    a.ub = p.W(OAC_WS_QNEW);
+    a.gauss = c.kind == OAC_KIND_GAUSS; a.std_bound = c.std_bound; a.delta_index = c.delta_index;
+    a.B = B; a.K = K; a.Da = Da;
+    a.seg_lo = 0; a.nseg = 1;
+    RUN_ROW(p, s, launch_det_seed_head_backward(a, s));
+    {
+      GemmBatch gb{};
+      add(gb, pol_head_dw(p, 0, G_DHEAD, G_H1P));
+      add(gb, pol_head_dx(p, 0, G_DHEAD, G_DH1P, G_H1P));
+      if (run_gemm(p, gb, s)) return 1;
+    }
+  } else {
+    {
+      GemmBatch gb{};
+      add(gb, critic_l1(p, q, G_H1N, G_H2N));
+      if (run_gemm(p, gb, s)) return 1;
+    }
+    const RowHead hn{p.W(G_H2N), q + L.q_last_w, q + L.q_last_b, p.W(OAC_WS_QN1), H};
+    if (c.kind == OAC_KIND_GAUSS) {
+      GaussSeedArgs a;
+      std::memset(&a, 0, sizeof(a));
+      a.qn = p.W(OAC_WS_QN1); a.qt = p.W(OAC_WS_QN2); a.hn = hn; a.std_bound = c.std_bound; a.B = B;
+      a.g = p.W(G_GQ); a.gt = p.W(G_GQ3); a.ub = p.W(OAC_WS_QNEW);
+      a.segs = 1;
+      RUN_ROW(p, s, launch_gauss_seed(a, s));
+    } else {
+      ParticleUbSeedArgs a;
+      std::memset(&a, 0, sizeof(a));
+      a.qn = p.W(OAC_WS_QN1); a.qt = p.W(OAC_WS_QN2); a.hn = hn; a.B = B; a.K = K;
+      a.delta_index = c.delta_index;
+      a.g = p.W(G_GQ); a.gt = p.W(G_GQ3); a.ub = p.W(OAC_WS_QNEW);
+      a.segs = 1;
+      RUN_ROW(p, s, launch_particle_ub_seed(a, s));
+    }
+    {
+      GemmBatch gb{};
+      add(gb, critic_last_dx(p, G_GQ, G_DH2N, G_H2N));
+      if (run_gemm(p, gb, s)) return 1;
+    }
+    {
+      GemmBatch gb{};
+      add(gb, critic_l1_dx(p, G_DH2N, G_DH1N, G_H1N));
+      if (run_gemm(p, gb, s)) return 1;
+    }
+    {
+      GemmBatch gb{};
+      add(gb, critic_act_dx(p, q, G_DH1N, G_DA, Da));
+      if (run_gemm(p, gb, s)) return 1;
+    }
+    {
+      DetHeadBwdArgs a;
+      std::memset(&a, 0, sizeof(a));
+      a.da[0] = p.W(G_DA); a.act[0] = p.W(OAC_WS_ACT1); a.dhead[0] = p.W(G_DHEAD);
+      a.nseg = 1; a.B = B; a.act_dim = Da;
+      RUN_ROW(p, s, launch_det_head_backward(a, s));
+    }
+    {
+      GemmBatch gb{};
+      add(gb, pol_head_dw(p, 0, G_DHEAD, G_H2P));
+      add(gb, pol_head_dx(p, 0, G_DHEAD, G_DH2P, G_H2P));
+      if (run_gemm(p, gb, s)) return 1;
+    }
+    {
+      GemmBatch gb{};
+      add(gb, pol_l1_dw(p, 0, G_DH2P, G_H1P));
+      add(gb, pol_l1_dx(p, 0, G_DH2P, G_DH1P, G_H1P));
+      if (run_gemm(p, gb, s)) return 1;
+    }
+  }
+  {
+    GemmBatch gb{};
+    add(gb, pol_l0_dw(p, 0, G_DH1P));
+    if (run_gemm(p, gb, s)) return 1;
+  }
+  PolicyOptAdamArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.a = policy_adam(p, 0, nullptr);
+  a.a.n = (long)L.pol_size;   // the policy block alone
+  a.a.state = opt; a.a.advance = 0;
+  a.ub = p.W(OAC_WS_QNEW); a.N = B;
+  a.part = p.W(G_OPT);
+  a.ticket = reinterpret_cast<unsigned*>(p.W(G_OPT) + 2 * kPolicyOptMaxBlocks);
+  a.hist = hist;
+  TIMED(p, K_ADAM, s, OAC_HIP_CHECK(launch_policy_opt_adam(a, s)));
+  p.launches++;
   return 0;
 }
 

@@ -291,6 +291,8 @@ struct GaussSeedArgs {
   float std_bound; int B;
   float* g; float* gt;                  // [B, 2] seeds of -mean(upper bound), -mean(q)
   float* ub;                            // [B] upper bound q + std_bound * std
+  int segs;                             // 0 / 3: both seeds; 1: the policy's (g, ub) only;
+                                        // 2: the target policy's (gt) only, qn not evaluated
 };
 hipError_t launch_gauss_seed(const GaussSeedArgs& a, hipStream_t s);
 
@@ -302,6 +304,7 @@ struct ParticleUbSeedArgs {            // particle_trainer.py:317-330, :339-348
   float* g;                             // [B, K] -1/B at the delta_index-th sorted head
   float* gt;                            // [B, K] -1/(B K) on every head (mean over particles)
   float* ub;                            // [B] upper bound sorted_k[delta_index]
+  int segs;                             // as GaussSeedArgs::segs
 };
 hipError_t launch_particle_ub_seed(const ParticleUbSeedArgs& a, hipStream_t s);
 
@@ -324,6 +327,7 @@ struct DetSeedHeadBwdArgs {
   int gauss; float std_bound;           // GAUSS: q + std_bound exp(log std)
   int delta_index;                      // PARTICLE_UB: the sorted particle maximised
   int B, K, Da;
+  int seg_lo, nseg;                     // segments [seg_lo, seg_lo + nseg) run (nseg 0: both)
 };
 hipError_t launch_det_seed_head_backward(const DetSeedHeadBwdArgs& a, hipStream_t s);
 
@@ -360,6 +364,29 @@ struct DdpgHeadBwdArgs {
   int B, H, Da;
 };
 hipError_t launch_ddpg_head_backward(const DdpgHeadBwdArgs& a, hipStream_t s);
+
+// global_opt (utils/core.py:64-137 optimize_policy): the sweep iteration's
+// obs-only gather, out[r, off + c] = replay[idx[r], off + c] for c < Do
+struct ObsGatherArgs {
+  const float* replay; long row_stride; const int* idx; int N, Do, off_obs; float* out;
+};
+hipError_t launch_obs_gather(const ObsGatherArgs& a, hipStream_t s);
+
+// ... and its policy-only Adam pass (adam.hip): split-K slabs reduced in
+// adam_flat_kernel's order, Adam with t = a.state->n_steps + 1 (a.state: the
+// sweep's own StepState-shaped counters; no Polyak), and in the same pass the
+// iteration's history row {-mean(ub), ||grad||_2} from per-workgroup partials
+// summed in workgroup order by the last workgroup to arrive (an integer
+// ticket, re-armed; no floating-point atomics), which also advances n_steps
+struct PolicyOptAdamArgs {
+  AdamArgs a;
+  const float* ub; int N;               // [N] the upper-bound column
+  float* part;                          // [2 * kPolicyOptMaxBlocks] partials
+  unsigned* ticket;                     // zeroed word
+  float* hist;                          // {loss, grad_norm}
+};
+constexpr int kPolicyOptMaxBlocks = 2048;
+hipError_t launch_policy_opt_adam(const PolicyOptAdamArgs& a, hipStream_t s);
 
 struct LogpSumArgs { const float* logp; int B; float target_entropy; AlphaState* alpha; };
 hipError_t launch_logp_sum(const LogpSumArgs& a, hipStream_t s);

@@ -206,6 +206,17 @@ static int validate(const oac_sac_config* c) {
               "activations as float4 columns), got %d", c->hidden);
     return 1;
   }
+  if (c->global_opt != 0 && c->global_opt != 1) {
+    set_error("global_opt must be 0 or 1, got %d", c->global_opt);
+    return 1;
+  }
+  if (c->global_opt && (!has_target_policy(c->kind) || c->world_size != 1)) {
+    static const char* const names[] = {"SAC", "PARTICLE", "GAUSS", "PARTICLE_UB", "DDPG"};
+    set_error("global_opt: kind %d (%s) with world_size %d is not supported; the policy sweep is "
+              "implemented for GAUSS (kind %d) and PARTICLE_UB (kind %d), single process",
+              c->kind, names[c->kind], c->world_size, OAC_KIND_GAUSS, OAC_KIND_PARTICLE_UB);
+    return 1;
+  }
   if (c->obs_dim < 1 || c->act_dim < 1 || c->act_dim > 32 || c->hidden < 1 || c->batch < 1) {
     set_error("bad dims obs=%d act=%d hidden=%d batch=%d", c->obs_dim, c->act_dim, c->hidden, c->batch);
     return 1;
@@ -334,6 +345,11 @@ int oac_sac_step_n(oac_sac* h, int flags, int n_steps, void* stream) {
   // (a kind without a data-parallel step issues direct launches only)
   if (!ops.step_phase && (flags & OAC_STEP_USE_GRAPH)) {
     set_error("DDPG (kind %d): OAC_STEP_USE_GRAPH is not supported, issue the step's launches "
+              "directly", p.c.kind);
+    return 1;
+  }
+  if (p.c.global_opt && (flags & OAC_STEP_USE_GRAPH)) {
+    set_error("global_opt (kind %d): OAC_STEP_USE_GRAPH is not supported, issue the step's launches "
               "directly", p.c.kind);
     return 1;
   }
@@ -530,6 +546,10 @@ int oac_sac_step_host_idx(oac_sac* h, const int64_t* idx, int64_t bc, int flags,
 int oac_sac_step_phase(oac_sac* h, int phase, int flags, void* stream) {
   if (!h) { set_error("null handle"); return 1; }
   if (no_dp_step(h->plan, "oac_sac_step_phase")) return 1;
+  if (h->plan.c.global_opt) {
+    set_error("oac_sac_step_phase: a global_opt handle (kind %d) is single-process", h->plan.c.kind);
+    return 1;
+  }
   return step_phase(h->plan, phase, flags, reinterpret_cast<hipStream_t>(stream));
 }
 
@@ -537,6 +557,10 @@ int oac_sac_set_allreduce(oac_sac* h, oac_allreduce_fn fn, void* ctx, int flags)
   if (!h) { set_error("null handle"); return 1; }
   SacPlan& p = h->plan;
   if (no_dp_step(p, "oac_sac_set_allreduce")) return 1;
+  if (p.c.global_opt) {
+    set_error("oac_sac_set_allreduce: a global_opt handle (kind %d) is single-process", p.c.kind);
+    return 1;
+  }
   if (fn && (flags & OAC_DP_OVERLAP) && !p.side) {
     OAC_HIP_CHECK(hipStreamCreateWithFlags(&p.side, hipStreamNonBlocking));
     OAC_HIP_CHECK(hipEventCreateWithFlags(&p.ev_fork, hipEventDisableTiming));
@@ -546,6 +570,48 @@ int oac_sac_set_allreduce(oac_sac* h, oac_allreduce_fn fn, void* ctx, int flags)
   p.ar_ctx = fn ? ctx : nullptr;
   p.ar_flags = fn ? flags : 0;
   return 0;
+}
+
+// ------------------------------------------------- global_opt policy sweep
+static int policy_opt_handle(oac_sac* h, const char* entry) {
+  if (!h) { set_error("null handle"); return 1; }
+  if (!h->plan.c.global_opt) {
+    set_error("%s: the handle (kind %d) was not created with global_opt = 1", entry, h->plan.c.kind);
+    return 1;
+  }
+  return 0;
+}
+
+int oac_sac_policy_opt_reset(oac_sac* h, const float* init_policy, void* stream) {
+  if (policy_opt_handle(h, "oac_sac_policy_opt_reset")) return 1;
+  SacPlan& p = h->plan;
+  if (!init_policy || !p.b.params) { set_error("oac_sac_policy_opt_reset: null init_policy / params"); return 1; }
+  OAC_HIP_CHECK(hipMemcpyAsync(p.b.params, init_policy, sizeof(float) * (size_t)p.L.pol_size,
+                               hipMemcpyDeviceToDevice, reinterpret_cast<hipStream_t>(stream)));
+  return 0;
+}
+
+int oac_sac_policy_opt_iter(oac_sac* h, const int64_t* idx, int64_t bc, void* opt_state,
+                            float* history_row, void* stream) {
+  if (policy_opt_handle(h, "oac_sac_policy_opt_iter")) return 1;
+  SacPlan& p = h->plan;
+  if (!opt_state || !history_row || !p.b.replay || !p.b.workspace) {
+    set_error("oac_sac_policy_opt_iter: null opt_state / history_row / replay / workspace");
+    return 1;
+  }
+  if (p.b.replay_rows < p.c.batch + (idx ? 0 : 1)) {
+    set_error("oac_sac_policy_opt_iter: replay_rows %lld too few for %d rows%s",
+              (long long)p.b.replay_rows, p.c.batch, idx ? "" : " read in place (needs one spare row)");
+    return 1;
+  }
+  const int* rows = nullptr;
+  if (idx) {   // staged through the host ring, copied to the device ring slot bc % ring_slots
+    if (!p.b.idx_ring) { set_error("oac_sac_policy_opt_iter: indices need an idx_ring"); return 1; }
+    if (stage_host_idx(h, idx, bc, stream, false)) return 1;
+    rows = p.b.idx_ring + (long)(bc % p.b.ring_slots) * p.c.batch;
+  }
+  return det_policy_opt_iter(p, rows, reinterpret_cast<StepState*>(opt_state), history_row,
+                             reinterpret_cast<hipStream_t>(stream));
 }
 
 int oac_sac_trace(oac_sac* h, int reset) {

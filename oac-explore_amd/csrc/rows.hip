@@ -824,19 +824,24 @@ __global__ void __launch_bounds__(256) gauss_targets_kernel(GaussTargetArgs p) {
 __global__ void __launch_bounds__(256) gauss_seed_kernel(GaussSeedArgs p) {
   __shared__ RowHeadLds hs;
   const int r0 = blockIdx.x * kRowBlock, r = r0 + threadIdx.x;
-  if (p.hn.h) {   // (the target policy's seed is constant: qt is never read)
+  const bool pol = p.segs != 2, tpol = p.segs != 1;   // (workgroup-uniform)
+  if (p.hn.h && pol) {   // (the target policy's seed is constant: qt is never read)
     row_heads(p.hn, 2, p.B, r0, hs);
     __syncthreads();
   }
   if (threadIdx.x >= kRowBlock || r >= p.B) return;
-  const float* qn = p.hn.h ? &hs.out[threadIdx.x][0] : p.qn + 2L * r;
   const float g0 = -(1.f / (float)p.B);
-  const float sd = expf(qn[1]);
-  p.ub[r] = __fadd_rn(qn[0], __fmul_rn(p.std_bound, sd));
-  p.g[2L * r] = g0;
-  p.g[2L * r + 1] = __fmul_rn(__fmul_rn(g0, p.std_bound), sd);
-  p.gt[2L * r] = g0;
-  p.gt[2L * r + 1] = 0.f;
+  if (pol) {
+    const float* qn = p.hn.h ? &hs.out[threadIdx.x][0] : p.qn + 2L * r;
+    const float sd = expf(qn[1]);
+    p.ub[r] = __fadd_rn(qn[0], __fmul_rn(p.std_bound, sd));
+    p.g[2L * r] = g0;
+    p.g[2L * r + 1] = __fmul_rn(__fmul_rn(g0, p.std_bound), sd);
+  }
+  if (tpol) {
+    p.gt[2L * r] = g0;
+    p.gt[2L * r + 1] = 0.f;
+  }
 }
 
 // particle_trainer.py policy losses through the post-step critic: the
@@ -846,16 +851,23 @@ __global__ void __launch_bounds__(256) particle_ub_seed_kernel(ParticleUbSeedArg
   __shared__ RowHeadLds hs;
   const int r0 = blockIdx.x * kRowBlock, r = r0 + threadIdx.x;
   const int K = p.K;
-  if (p.hn.h) {   // (the target policy's seed is constant: qt is never read)
+  const bool pol = p.segs != 2, tpol = p.segs != 1;   // (workgroup-uniform)
+  if (p.hn.h && pol) {   // (the target policy's seed is constant: qt is never read)
     row_heads(p.hn, K, p.B, r0, hs);
     __syncthreads();
   }
   if (threadIdx.x >= kRowBlock || r >= p.B) return;
+  const float g0 = -(1.f / (float)p.B);
+  if (!pol) {
+#pragma unroll
+    for (int i = 0; i < kMaxHeads; ++i)
+      if (i < K) p.gt[(long)r * K + i] = g0 / (float)K;
+    return;
+  }
   float v[kMaxHeads];
   int ix[kMaxHeads];
   load_row16(p.hn.h ? &hs.out[threadIdx.x][0] : p.qn + (long)r * K, K, v, ix);
   sort16(v, ix);
-  const float g0 = -(1.f / (float)p.B);
   int sel = ix[0];
   float ub = v[0];
 #pragma unroll
@@ -865,7 +877,7 @@ __global__ void __launch_bounds__(256) particle_ub_seed_kernel(ParticleUbSeedArg
   for (int i = 0; i < kMaxHeads; ++i) {
     if (i < K) {
       p.g[(long)r * K + i] = (i == sel) ? g0 : 0.f;
-      p.gt[(long)r * K + i] = g0 / (float)K;
+      if (tpol) p.gt[(long)r * K + i] = g0 / (float)K;
     }
   }
   p.ub[r] = ub;
@@ -898,7 +910,7 @@ __global__ void __launch_bounds__(256) det_seed_head_backward_kernel(DetSeedHead
   __shared__ RowHeadLds hs;
   __shared__ float sg[kRowBlock][kMaxHeads];
   __shared__ float sdh[kRowBlock][kDshChunk + 1];
-  const int seg = blockIdx.y;
+  const int seg = p.seg_lo + blockIdx.y;
   const int r0 = blockIdx.x * kRowBlock;
   const int K = p.K, H = p.hn.H, Da = p.Da, B = p.B;
   const float g0 = -(1.f / (float)B);
@@ -1096,8 +1108,11 @@ hipError_t launch_det_seed_head_backward(const DetSeedHeadBwdArgs& a, hipStream_
     return hipErrorInvalidValue;
   for (int g = 0; g < 2; ++g)
     if (!a.act[g] || !a.dhead[g]) return hipErrorInvalidValue;
-  OAC_LAUNCH(det_seed_head_backward_kernel, dim3((a.B + kRowBlock - 1) / kRowBlock, 2), dim3(256),
-             0, s, a);
+  DetSeedHeadBwdArgs b = a;
+  if (b.nseg == 0) { b.seg_lo = 0; b.nseg = 2; }
+  if (b.seg_lo < 0 || b.nseg < 1 || b.seg_lo + b.nseg > 2) return hipErrorInvalidValue;
+  OAC_LAUNCH(det_seed_head_backward_kernel, dim3((a.B + kRowBlock - 1) / kRowBlock, b.nseg),
+             dim3(256), 0, s, b);
   return hipGetLastError();
 }
 hipError_t launch_det_head_backward(const DetHeadBwdArgs& a, hipStream_t s) {

@@ -48,7 +48,9 @@ struct SacPlan : PlanBase {
   bool inline_ok = false;
 
   float* W(int id) const { return b.workspace + ws[id].off; }
-  float* X() const { return W(OAC_WS_BATCH) + (long)slot * c.batch * c.row_stride; }
+  // the global_opt sweep's rows (det_plan.hip): the batch copy, or the replay in place
+  float* x_rows = nullptr;
+  float* X() const { return x_rows ? x_rows : W(OAC_WS_BATCH) + (long)slot * c.batch * c.row_stride; }
   float* E1() const { return W(OAC_WS_EPS1) + (long)slot * c.batch * c.act_dim; }
   float* E2() const { return W(OAC_WS_EPS2) + (long)slot * c.batch * c.act_dim; }
   float* P(int64_t off) const { return b.params + off; }
@@ -111,6 +113,15 @@ inline AdamArgs policy_adam(SacPlan& p, int reduce_only, AlphaState* commit) {
   a.state = p.state(); a.advance = 1; a.alpha = commit;
   a.gscale = reduce_only < 0 ? 1.f / (float)c.world_size : 1.f;
   a.reduce_only = reduce_only > 0;
+  return a;
+}
+
+// global_opt step: the policy group's update covers the target_policy block only
+inline AdamArgs tpol_adam(SacPlan& p) {
+  AdamArgs a = policy_adam(p, 0, nullptr);
+  const long tp = (long)p.L.tpol_base;
+  a.p += tp; a.g += tp; a.m += tp; a.v += tp; a.gslab += tp;
+  a.n = (long)p.L.pol_size;
   return a;
 }
 
@@ -471,6 +482,9 @@ int particle_ws_alias(int which);
 void det_layout_workspace(SacPlan& p);
 int det_run_step(SacPlan& p, int flags, hipStream_t s, int i, int n);
 int det_step_phase(SacPlan& p, int phase, int flags, hipStream_t s);
+// one iteration of the global_opt sweep (rows: the iteration's device index slot, or null =
+// rows 0..N-1 of the replay in place)
+int det_policy_opt_iter(SacPlan& p, const int* rows, StepState* opt, float* hist, hipStream_t s);
 // DDPGTrainer: one critic, deterministic policy, no target_policy block
 // (ddpg_plan.hip); single-process only
 void ddpg_layout_workspace(SacPlan& p);

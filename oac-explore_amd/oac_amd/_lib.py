@@ -80,7 +80,7 @@ class SacConfig(ctypes.Structure):
         ("std_soft_update", ctypes.c_int), ("std_soft_prob", ctypes.c_float),
         ("mean_update", ctypes.c_int), ("delta_index", ctypes.c_int),
         ("rescale_spread", ctypes.c_float), ("freeze_q_bias", ctypes.c_int),
-        ("n_hidden", ctypes.c_int),
+        ("n_hidden", ctypes.c_int), ("global_opt", ctypes.c_int),
     ]
 
 
@@ -119,6 +119,9 @@ _SIGS = {
                                       ctypes.c_void_p]),
     "oac_sac_step_phase": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
                                           ctypes.c_void_p]),
+    "oac_sac_policy_opt_reset": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "oac_sac_policy_opt_iter": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
+                                               ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "oac_sac_set_host_ring": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
     "oac_sac_host_ring": (ctypes.c_void_p, [ctypes.c_void_p]),
     "oac_sac_step_host_idx": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,

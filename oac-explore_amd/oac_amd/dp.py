@@ -130,6 +130,10 @@ class _DataParallel:
 
     def __init__(self, *args, process_group=None, capture=None, force_collectives=False,
                  force_overlap=False, transport=None, **kwargs):
+        if kwargs.get("global_opt"):
+            raise NotImplementedError(
+                "the data-parallel trainers do not implement global_opt (the policy sweep, "
+                "optimize_policies, is single-process); unsupported: ['global_opt']")
         if not dist.is_initialized():
             raise RuntimeError("DataParallelSACTrainer needs torch.distributed initialised")
         self.pg = process_group

@@ -39,13 +39,13 @@ class GaussianTrainer(_TargetPolicyTrainer):
                  rescale_targets_around_mean=False,
                  device=None, seed=0, use_graph=False, gemm_cfg=-1):
         unsupported = dict(share_layers=not share_layers, deterministic=not deterministic,
-                           ensemble=ensemble, global_opt=global_opt)
+                           ensemble=ensemble)
         bad = [k for k, v in unsupported.items() if v]
         if bad:
             raise NotImplementedError(
                 "oac_amd.GaussianTrainer implements the g-oac recipe configuration "
                 "(share_layers=True, deterministic policy, counts / std_soft_update / "
-                f"mean_update / use_target_policy, no ensemble / global-opt); unsupported: {bad}")
+                f"mean_update / use_target_policy, global_opt, no ensemble); unsupported: {bad}")
         assert not counts or not std_soft_update   # gaussian_trainer.py:88
         self._common_init(device, soft_target_tau, target_update_period, deterministic,
                           discount, reward_scale, policy_lr, qf_lr, use_graph, seed, gemm_cfg)
@@ -76,8 +76,11 @@ class GaussianTrainer(_TargetPolicyTrainer):
         qb = np.array([mean, np.log(std)])
         ref_q = q_producer(bias=qb, positive=[False, True], train_bias=train_bias)
         ref_qt = q_producer(bias=qb, positive=[False, True], train_bias=train_bias)
+        ref_init = policy_producer() if global_opt else None
         ref_tp = policy_producer()
+        ref_init_tp = policy_producer() if global_opt else None
         self._build(ref_pol, ref_q, ref_qt, ref_tp, policy_lr, qf_lr)
+        self._make_init_policies(ref_init, ref_init_tp)
         self._make_target_policy_network(policy_producer)
         self.q, self.q_target = self.qfs[0], self.tfs[0]
         self.q_optimizer = self.qf_optimizers[0]
@@ -107,7 +110,8 @@ class GaussianTrainer(_TargetPolicyTrainer):
         st["STD Loss"] = np.float32(np.mean(v["sqe1"][:, 1]))
         self._stats(st, "Q STD Predictions", std_preds)
         self._stats(st, "Q STD Target", v["y"][:, 1:2])
-        st["Policy Loss"] = np.mean(v["qnew"])
+        if not self.global_opt:   # (:422 / :418: the step has no policy loss)
+            st["Policy Loss"] = np.mean(v["qnew"])
         self._stats(st, "Policy mu", v["head3"][:, :Da])
         self._stats(st, "Policy log std", np.clip(v["head3"][:, Da:], -20, 2))
         self.eval_statistics = st

@@ -38,14 +38,14 @@ class ParticleTrainer(_TargetPolicyTrainer):
                  rescale_targets_around_mean=False,
                  device=None, seed=0, use_graph=False, gemm_cfg=-1):
         unsupported = dict(share_layers=not share_layers, deterministic=not deterministic,
-                           ensemble=ensemble, global_opt=global_opt)
+                           ensemble=ensemble)
         bad = [k for k, v in unsupported.items() if v]
         if bad:
             raise NotImplementedError(
                 "oac_amd.ParticleTrainer implements the p-oac recipe configuration "
                 "(share_layers=True, deterministic policy, counts / std_soft_update / "
                 "mean_update / rescale_targets_around_mean / train_bias / "
-                f"use_target_policy, no ensemble / global-opt); unsupported: {bad}")
+                f"use_target_policy, global_opt, no ensemble); unsupported: {bad}")
         assert not counts or not std_soft_update   # particle_trainer.py:92
         self._common_init(device, soft_target_tau, target_update_period, deterministic,
                           discount, reward_scale, policy_lr, qf_lr, use_graph, seed, gemm_cfg)
@@ -83,8 +83,11 @@ class ParticleTrainer(_TargetPolicyTrainer):
         init_values = np.linspace(q_min, q_max, n_estimators)
         ref_q = q_producer(bias=init_values, train_bias=train_bias)
         q_producer(bias=init_values, train_bias=train_bias)
+        ref_init = policy_producer() if global_opt else None
         ref_tp = policy_producer()
+        ref_init_tp = policy_producer() if global_opt else None
         self._build(ref_pol, ref_q, ref_q, ref_tp, policy_lr, qf_lr)
+        self._make_init_policies(ref_init, ref_init_tp)
         self._make_target_policy_network(policy_producer)
 
     def _make_cfg(self, batch):
@@ -117,7 +120,8 @@ class ParticleTrainer(_TargetPolicyTrainer):
             st[f"QF{i} Loss"] = losses[i]
             self._stats(st, f"Q{i}Predictions", sorted_qs[i])
             self._stats(st, f"Q{i}Targets", tq[:, i:i + 1])
-        st["Policy Loss"] = np.mean(v["qnew"])
+        if not self.global_opt:   # (:422 / :418: the step has no policy loss)
+            st["Policy Loss"] = np.mean(v["qnew"])
         self._stats(st, "Policy mu", v["head3"][:, :Da])
         self._stats(st, "Policy log std", np.clip(v["head3"][:, Da:], -20, 2))
         self.eval_statistics = st

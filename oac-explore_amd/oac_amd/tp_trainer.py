@@ -7,15 +7,33 @@ trained ``target_policy`` -- g-oac ``GaussianTrainer``
 optimizer set and the same snapshot keys; their steps run in liboac_amd
 (csrc/det_plan.hip) over the arena [policy | target_policy | critic].
 """
+import ctypes
+import random
 from collections import OrderedDict
 
 import numpy as np
 import torch
 
+from . import _lib
+from ._lib import check, stream_ptr
 from .networks import ArenaFlattenMlp, ArenaTanhGaussianPolicy
 from .trainer import AdamStateView, _ArenaTrainer, _dims_from_state, _twin_views, _plain_stats
 
 _LOG_STD_HEAD = ("last_fc_log_std.weight", "last_fc_log_std.bias")
+
+
+def shuffle_gather_indices(n):
+    """``J`` with ``new[i] = old[J[i]]`` for one ``random.shuffle`` of an n-row
+    2-D numpy array as utils/core.py:74 performs it -- drawn from the global
+    ``random`` stream exactly as ``shuffle`` draws (``_randbelow(i + 1)`` for
+    i = n-1 .. 1).  Python's swap ``x[i], x[j] = x[j], x[i]`` evaluates two row
+    VIEWS on the right, so row j is copied over row i and row i's value is
+    lost: the shuffle duplicates rows instead of permuting them.  j <= i and
+    position j is overwritten only later, so each shuffle is a gather."""
+    below = getattr(random.shuffle.__self__, "_randbelow", None) or random.randrange
+    J = np.zeros(n, np.int64)
+    J[:0:-1] = [below(i + 1) for i in range(n - 1, 0, -1)]
+    return J
 
 
 class _TargetPolicyTrainer(_ArenaTrainer):
@@ -59,11 +77,15 @@ class _TargetPolicyTrainer(_ArenaTrainer):
         # deterministic policies: the log-std heads never get a gradient
         no_grad = [i for i, n in enumerate(names) if n in _LOG_STD_HEAD]
 
-        def popt(mod):
+        def popt(mod, step_source=None):
             return AdamStateView(self, list(mod.parameters()), tw(self.adam_m, mod),
                                  tw(self.adam_v, mod), policy_lr, (0.9, 0.999), 1e-8,
-                                 no_grad=no_grad)
-        self.policy_optimizer = popt(self.policy)
+                                 no_grad=no_grad, step_source=step_source)
+        # global_opt: the policy's optimizer is stepped by optimize_policies
+        # alone (utils/core.py:98), so its `step` counts sweep iterations
+        self._policy_opt_steps = 0
+        self.policy_optimizer = popt(
+            self.policy, (lambda: self._policy_opt_steps) if self.global_opt else None)
         self.target_policy_optimizer = popt(self.target_policy)
         q_no_grad = [] if self.train_bias else \
             [i for i, (n, _) in enumerate(qf.named_parameters()) if n == "last_fc.bias"]
@@ -99,12 +121,136 @@ class _TargetPolicyTrainer(_ArenaTrainer):
     def _next_policy_ptr(self):
         return None if getattr(self, "_tpn", None) is None else self._tpn.data_ptr()
 
+    # ------------------------------------------------------------ global_opt
+    def _make_init_policies(self, ref_init, ref_init_tp):
+        """global_opt (gaussian_trainer.py:143-151, particle_trainer.py:139-144):
+        ``init_policy`` / ``init_target_policy``, two policy_producer()
+        networks that are never trained -- frozen policy-shaped blocks outside
+        the Adam arena; like the reference's, neither in ``networks`` nor in
+        the snapshot.  optimize_policies restarts the policy from init_policy."""
+        self.policy_opt_history = None
+        self._sweep = None
+        if not self.global_opt:
+            return
+        if self.use_graph:
+            raise NotImplementedError("global_opt with use_graph=True: a global_opt step is "
+                                      "issued as direct launches; unsupported: ['use_graph']")
+        lay = self.layout
+        mods = []
+        for ref in (ref_init, ref_init_tp):
+            block = torch.zeros(int(lay.pol_size), dtype=torch.float32, device=self.device)
+            mod = ArenaTanhGaussianPolicy(block, 0, lay, self.obs_dim, self.act_dim, self.hidden)
+            mod.load_state_dict({k: v.detach() for k, v in ref.state_dict().items()})
+            mods.append((block, mod))
+        (self._init_pol, self.init_policy), (self._init_tpol, self.init_target_policy) = mods
+        # the sweep's own counters (oac_sac_policy_opt_iter's opt_state): 64 bytes
+        self._popt_state = torch.zeros(8, dtype=torch.int64, device=self.device)
+
+    def _set_policy_opt_steps(self, n):
+        self._policy_opt_steps = int(n)
+        if self.global_opt:
+            self._popt_state.zero_()
+            self._popt_state[0] = self._policy_opt_steps
+
+    _SWEEP_SLOTS = 32   # index ring slots (two completion chunks: staging runs 16 iterations ahead)
+
+    def _sweep_rows(self, buffer):
+        """(rows [>= N + 1, row_stride] on the device, N): the buffer's own
+        device storage, or a get_dataset() array uploaded once.  One spare row
+        behind the N lets shuffle='none' read the rows in place."""
+        stride = self.rows["row_stride"]
+        st = getattr(buffer, "_storage", None)
+        if torch.is_tensor(st) and st.is_cuda and st.shape[1] == stride:
+            N = int(buffer._size)
+            if st.shape[0] > N:
+                return st, N
+            spare = torch.zeros(N + 1, stride, dtype=torch.float32, device=self.device)
+            spare[:N].copy_(st[:N])
+            return spare, N
+        data = buffer.get_dataset()
+        data = torch.as_tensor(np.asarray(data) if not torch.is_tensor(data) else data)
+        N = int(data.shape[0])
+        rows = torch.zeros(N + 1, stride, dtype=torch.float32, device=self.device)
+        o = self.rows["off_obs"]
+        rows[:N, o:o + self.obs_dim].copy_(data.reshape(N, self.obs_dim).to(torch.float32))
+        return rows, N
+
+    def _sweep_plan(self, rows, N):
+        """The one sweep plan (batch = N): a new N or store replaces it."""
+        key = (N, rows.data_ptr())
+        if self._sweep is not None and self._sweep[0] == key:
+            self._sweep[1].rows = rows
+            return self._sweep[1]
+        if self._sweep is not None:
+            old = self._sweep[1]
+            self._sweep = None
+            torch.cuda.current_stream(self.device).wait_stream(self.stream)
+            torch.cuda.synchronize(self.device)   # (its launches read its workspace)
+            self._plans.pop(old.key, None)
+            check(_lib.lib().oac_sac_destroy(old.handle))
+        S = self._SWEEP_SLOTS
+        ring = torch.zeros(S * N, dtype=torch.int32, device=self.device)
+        plan = self._plan(N, replay=rows, idx=ring, ring_slots=S)
+        check(_lib.lib().oac_sac_set_host_ring(plan.handle, None))
+        plan.rings, plan.rows, plan.bc = (ring,), rows, 0
+        self._sweep = (key, plan)
+        return plan
+
+    def optimize_policies(self, buffer, out_dir='', epoch=0, save_fig=False, *, iterations=150,
+                          shuffle="reference"):
+        """rl_algorithm.py:169-171 -> utils/core.py:64-137 optimize_policy: the
+        policy restarts from ``init_policy`` and takes ``iterations`` Adam steps
+        (its own optimizer: moments and step count carry on) on -mean(upper
+        bound of the frozen critic) over the whole replay as one batch.
+        shuffle='reference': each iteration's rows are what the reference's
+        ``random.shuffle(dataset)`` leaves (shuffle_gather_indices; the global
+        ``random`` stream advances exactly as there), staged while the GPU runs
+        the previous iteration; 'none': rows 0..N-1 every iteration, no host
+        work.  ``policy_opt_history`` = {'loss', 'grad_norm'} per iteration,
+        read back once at the end."""
+        if not self.global_opt:
+            raise RuntimeError("optimize_policies needs a trainer built with global_opt=True")
+        if save_fig:
+            raise NotImplementedError("save_fig: plotting is out of scope; the curves are in "
+                                      "trainer.policy_opt_history")
+        if shuffle not in ("reference", "none"):
+            raise ValueError(f"shuffle {shuffle!r}: 'reference' or 'none'")
+        iterations = int(iterations)
+        rows, N = self._sweep_rows(buffer)
+        if N < 1 or iterations < 1:
+            self.policy_opt_history = dict(loss=[], grad_norm=[])
+            return None
+        plan = self._sweep_plan(rows, N)
+        hist = torch.zeros(iterations, 2, dtype=torch.float32, device=self.device)
+        L = _lib.lib()
+        opt = ctypes.c_void_p(self._popt_state.data_ptr())
+
+        def go(sp):
+            check(L.oac_sac_policy_opt_reset(plan.handle, ctypes.c_void_p(self._init_pol.data_ptr()),
+                                             sp))
+            idx = np.arange(N, dtype=np.int64)
+            for k in range(iterations):
+                row = ctypes.c_void_p(hist.data_ptr() + 8 * k)
+                if shuffle == "none":
+                    check(L.oac_sac_policy_opt_iter(plan.handle, None, 0, opt, row, sp))
+                    continue
+                idx = idx[shuffle_gather_indices(N)]
+                check(L.oac_sac_policy_opt_iter(plan.handle, ctypes.c_void_p(idx.ctypes.data),
+                                                plan.bc, opt, row, sp))
+                plan.bc += 1
+        self._on_stream(go)
+        self._policy_opt_steps += iterations
+        h = hist.cpu().numpy()
+        self.policy_opt_history = dict(loss=h[:, 0].tolist(), grad_norm=h[:, 1].tolist())
+        return None
+
     def _make_cfg(self, batch):
         c = super()._make_cfg(batch)
         c.std_soft_update = int(bool(self.std_soft_update))
         c.std_soft_prob = float(self.std_soft_update_prob)
         c.mean_update = int(bool(self.mean_update))
         c.freeze_q_bias = int(not self.train_bias)
+        c.global_opt = int(bool(self.global_opt))
         return c
 
     @staticmethod
@@ -154,6 +300,9 @@ class _TargetPolicyTrainer(_ArenaTrainer):
         """gaussian_trainer.py:484-517 / particle_trainer.py:480-505."""
         self.policy.load_state_dict(ss["policy_state_dict"])
         self.policy_optimizer.load_state_dict(ss["policy_optim_state_dict"])
+        if self.global_opt:   # the policy optimizer's own step count, back into the device counter
+            steps = [int(v["step"]) for v in ss["policy_optim_state_dict"]["state"].values()]
+            self._set_policy_opt_steps(max(steps) if steps else 0)
         for i in range(len(ss["qfs_state_dicts"])):
             self.qfs[i].load_state_dict(ss["qfs_state_dicts"][i])
             self.qf_optimizers[i].load_state_dict(ss["qfs_optims_state_dicts"][i])

@@ -94,8 +94,12 @@ class AdamStateView:
     update itself is fused into the step kernels; ``step``/``zero_grad`` are
     no-ops kept for interface compatibility."""
 
-    def __init__(self, trainer, params, m_views, v_views, lr, betas, eps, no_grad=()):
+    def __init__(self, trainer, params, m_views, v_views, lr, betas, eps, no_grad=(),
+                 step_source=None):
         self._t, self.params = trainer, params
+        # `step` of this optimizer's state: the trainer's step count, or (an
+        # optimizer stepped elsewhere: global_opt's policy) its own source
+        self._step = step_source or (lambda: trainer._n_train_steps_total)
         self.m, self.v = m_views, v_views
         # parameters that never receive a gradient (torch Adam keeps no state
         # for them; their m / v stay zero here, so the update is exactly 0)
@@ -110,7 +114,7 @@ class AdamStateView:
         pass
 
     def state_dict(self):
-        t = self._t._n_train_steps_total
+        t = self._step()
         state = {}
         if t > 0:
             for i, (m, v) in enumerate(zip(self.m, self.v)):
