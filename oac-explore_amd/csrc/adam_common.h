@@ -11,14 +11,23 @@ namespace oac {
 struct AdamConsts { float b1, omb1, b2, omb2, step_size, sbc2, eps, tau, omtau; bool polyak; };
 
 // bias corrections of step t (torch-1.4 Adam: bias_correction1/2 in double)
-__device__ __forceinline__ void bias_corrections(const StepState* st, long long t, double beta1,
-                                                 double beta2, double& bc1, double& sbc2) {
-  if (st->bc_t == t) {   // published by the step's first launch (same formula)
-    bc1 = st->bc1; sbc2 = st->sbc2;
+// from the published words of StepState, as loaded (bc_t, bc1, sbc2)
+__device__ __forceinline__ void bias_corrections_of(long long bc_t, double pub_bc1, double pub_sbc2,
+                                                    long long t, double beta1, double beta2,
+                                                    double& bc1, double& sbc2) {
+  if (bc_t == t) {   // published by the step's first launch (same formula)
+    bc1 = pub_bc1; sbc2 = pub_sbc2;
   } else {
     bc1 = 1.0 - pow(beta1, (double)t);
     sbc2 = sqrt(1.0 - pow(beta2, (double)t));
   }
+}
+// (the three words requested together: one round trip to the StepState line)
+__device__ __forceinline__ void bias_corrections(const StepState* st, long long t, double beta1,
+                                                 double beta2, double& bc1, double& sbc2) {
+  const long long bc_t = st->bc_t;
+  const double pub_bc1 = st->bc1, pub_sbc2 = st->sbc2;
+  bias_corrections_of(bc_t, pub_bc1, pub_sbc2, t, beta1, beta2, bc1, sbc2);
 }
 
 // block 0, thread 0 of a step's first launch (no kernel of that launch reads it)
@@ -30,12 +39,27 @@ __device__ __forceinline__ void publish_step_consts(StepState* st, double beta1,
   st->bc_t = t;
 }
 
-__device__ __forceinline__ AdamConsts adam_consts(const StepState* st, int advance, double lr,
-                                                  double beta1, double beta2, double eps,
-                                                  const float* target, float tau, int period) {
-  const long long nsteps = advance ? st->t_snapshot : st->n_steps;
-  double bc1, sbc2;
-  bias_corrections(st, nsteps + 1, beta1, beta2, bc1, sbc2);
+// adam_consts in two halves, for a kernel that wants the StepState line on its
+// way while it does other work: the words adam_consts reads, as loaded ...
+struct AdamStateIn { long long nsteps, bc_t; double bc1, sbc2; };
+
+// (no launch writes a field another block of it reads, so the loads may sit
+// anywhere in the kernel.  Scalar loads through the constant address space:
+// the values are workgroup-uniform and unchanged for the whole launch.)
+__device__ __forceinline__ AdamStateIn adam_state_request(const StepState* st, int advance) {
+  const __attribute__((address_space(4))) StepState* cs =
+      (const __attribute__((address_space(4))) StepState*)(uintptr_t)st;
+  AdamStateIn s;
+  s.nsteps = advance ? cs->t_snapshot : cs->n_steps;
+  s.bc_t = cs->bc_t; s.bc1 = cs->bc1; s.sbc2 = cs->sbc2;
+  return s;
+}
+
+// ... and the constants formed from them: from step count nsteps and its
+// bias corrections ...
+__device__ __forceinline__ AdamConsts adam_consts_of(long long nsteps, double bc1, double sbc2, double lr,
+                                                     double beta1, double beta2, double eps,
+                                                     const float* target, float tau, int period) {
   AdamConsts c;
   c.b1 = (float)beta1; c.omb1 = (float)(1.0 - beta1);
   c.b2 = (float)beta2; c.omb2 = (float)(1.0 - beta2);
@@ -45,6 +69,20 @@ __device__ __forceinline__ AdamConsts adam_consts(const StepState* st, int advan
   c.tau = tau; c.omtau = (float)(1.0 - (double)tau);
   c.polyak = target && (period <= 1 || (nsteps % period) == 0);
   return c;
+}
+// ... with bias_corrections' formula and branch
+__device__ __forceinline__ AdamConsts adam_consts_finish(const AdamStateIn& s, double lr, double beta1,
+                                                         double beta2, double eps, const float* target,
+                                                         float tau, int period) {
+  double bc1, sbc2;
+  bias_corrections_of(s.bc_t, s.bc1, s.sbc2, s.nsteps + 1, beta1, beta2, bc1, sbc2);
+  return adam_consts_of(s.nsteps, bc1, sbc2, lr, beta1, beta2, eps, target, tau, period);
+}
+
+__device__ __forceinline__ AdamConsts adam_consts(const StepState* st, int advance, double lr,
+                                                  double beta1, double beta2, double eps,
+                                                  const float* target, float tau, int period) {
+  return adam_consts_finish(adam_state_request(st, advance), lr, beta1, beta2, eps, target, tau, period);
 }
 
 // m = b1 m + (1-b1) g ; v = b2 v + (1-b2) g g ; p += -(lr/bc1) m / (sqrt(v)/sqrt(bc2) + eps)

@@ -156,8 +156,15 @@ __device__ __forceinline__ void k_dispatch(const GemmTask& t, int m0, int n0, in
 // EPI_GRAD with the fused optimizer: p, m, v (and the Polyak target) of the element.
 struct EpiIn { float xb, xa, am, av, at, s; };
 
-__device__ __forceinline__ EpiIn epi_prefetch(const GemmBatch& batch, const GemmTask& t, int m,
-                                              int n) {
+// The fused optimizer as a tile block sees it: whether it runs and which
+// counter it reads come from the launch header's flags (registers at kernel
+// entry), its arguments are read in place in the kernel-argument segment.
+struct EpiAdam {
+  bool fuse, advance;
+  const AdamArgs& a;
+};
+
+__device__ __forceinline__ EpiIn epi_prefetch(const EpiAdam& ea, const GemmTask& t, int m, int n) {
   EpiIn x{0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   const bool in = m < t.M && n < t.N;
   const int mc = in ? m : 0, nc = in ? n : 0;
@@ -170,11 +177,11 @@ __device__ __forceinline__ EpiIn epi_prefetch(const GemmBatch& batch, const Gemm
       break;
     }
     case EPI_GRAD:
-      if (batch.fuse_adam && !t.no_adam) {
+      if (ea.fuse && !t.no_adam) {
         const float* g = (t.b_ones && nc == t.N - 1) ? t.bias_grad + mc : t.C + (long)mc * t.ldc + nc;
-        const long i = g - batch.adam.g;
-        x.xb = batch.adam.p[i]; x.am = batch.adam.m[i]; x.av = batch.adam.v[i];
-        if (batch.adam.target) x.at = batch.adam.target[i];
+        const long i = g - ea.a.g;
+        x.xb = ea.a.p[i]; x.am = ea.a.m[i]; x.av = ea.a.v[i];
+        if (ea.a.target) x.at = ea.a.target[i];
       }
       break;
     case EPI_BIAS: case EPI_BIAS_RELU: case EPI_BIAS_RANK_RELU:
@@ -188,7 +195,7 @@ __device__ __forceinline__ EpiIn epi_prefetch(const GemmBatch& batch, const Gemm
   return x;
 }
 
-__device__ __forceinline__ void epi_one(const GemmBatch& batch, const AdamConsts& ac,
+__device__ __forceinline__ void epi_one(const EpiAdam& ea, const AdamConsts& ac,
                                         const GemmTask& t, int m, int n, float acc, EpiIn x,
                                         const float* lds_u, const float* lds_v, int mt, int nt) {
   if (m >= t.M || n >= t.N) return;
@@ -198,14 +205,14 @@ __device__ __forceinline__ void epi_one(const GemmBatch& batch, const AdamConsts
     case EPI_GRAD: {
       float* g = (t.b_ones && n == t.N - 1) ? t.bias_grad + m : t.C + o;
       *g = acc;
-      if (batch.fuse_adam && !t.no_adam) {   // adam_elem on the prefetched p, m, v, target
-        const long i = g - batch.adam.g;
+      if (ea.fuse && !t.no_adam) {   // adam_elem on the prefetched p, m, v, target
+        const long i = g - ea.a.g;
         float p = x.xb, m = x.am, v = x.av;
         adam1(ac, p, acc, m, v);
-        (batch.adam.p_out ? batch.adam.p_out : batch.adam.p)[i] = p;
-        if (!batch.adam.preview) {
-          batch.adam.m[i] = m; batch.adam.v[i] = v;
-          if (ac.polyak) batch.adam.target[i] = polyak1(ac, x.at, p);
+        (ea.a.p_out ? ea.a.p_out : ea.a.p)[i] = p;
+        if (!ea.a.preview) {
+          ea.a.m[i] = m; ea.a.v[i] = v;
+          if (ac.polyak) ea.a.target[i] = polyak1(ac, x.at, p);
         }
       }
       break;
@@ -237,19 +244,56 @@ __device__ __forceinline__ void epi_one(const GemmBatch& batch, const AdamConsts
   }
 }
 
-// Launch header as leading scalar kernel arguments: with
-// -mllvm -amdgpu-kernarg-preload-count they arrive in SGPRs, so a block finds
-// its task without a dependent kernarg round trip; only the task record itself
-// is then loaded (one scalar round trip).
-struct GemmHead { int total_tiles, publish, tb1, tb2, tb3, tb4, tb5, tb6, tb7; };
+// Launch header as leading scalar kernel arguments (14 dwords of the 16 that
+// -mllvm -amdgpu-kernarg-preload-count delivers in SGPRs): everything a block
+// needs to find its role and its task, and the StepState pointer, so no branch
+// of the prologue and no address of its first loads waits on the
+// kernel-argument segment.  A tile block's first scalar loads are its task
+// record and, with it, the StepState words of adam_consts (and the index-slot
+// form's batch_counter).  The record still arrives in two groups: 75 dwords
+// of record, this header and the StepState words do not fit the 102 SGPRs at
+// once, and pinning every field to one group made the compiler issue four,
+// each with a spill and a wait (profiles/r07/small_prologue_isa.txt).
+enum : int {
+  kHeadRing = 1,      // rg.ring set: rows through the index slot (or inline, kHeadInl)
+  kHeadInl = 2,       // the indices are in the kernel arguments (gemm_small_kernel_inl)
+  kHeadFuse = 4,      // batch.fuse_adam
+  kHeadCopy = 8,      // batch.adam.copy_src set: the side optimizer blocks copy
+  kHeadAdvance = 16,  // batch.adam.advance
+};
+struct GemmHead {
+  int total_tiles, publish, tb1, tb2, tb3, tb4, tb5, tb6, tb7;
+  int adam_blocks, side_blocks, flags;
+  const StepState* state;   // adam.state (kHeadFuse) / rg.state (kHeadRing): one StepState per launch
+};
+#define OAC_HEAD_PARAMS                                                                              \
+  int total_tiles, int publish, int tb1, int tb2, int tb3, int tb4, int tb5, int tb6, int tb7,       \
+      int adam_blocks, int side_blocks, int flags, const StepState *state
+#define OAC_HEAD_OF_PARAMS \
+  GemmHead{total_tiles, publish, tb1, tb2, tb3, tb4, tb5, tb6, tb7, adam_blocks, side_blocks, flags, state}
+#define OAC_HEAD_ARGS(h)                                                                             \
+  (h).total_tiles, (h).publish, (h).tb1, (h).tb2, (h).tb3, (h).tb4, (h).tb5, (h).tb6, (h).tb7,       \
+      (h).adam_blocks, (h).side_blocks, (h).flags, (h).state
 
-static GemmHead gemm_head(const GemmBatch& b) {
+// (b.adam_blocks set; inl: the launch carries the indices in its arguments)
+static GemmHead gemm_head(const GemmBatch& b, bool inl = false) {
   GemmHead h;
   int tb[8];
   for (int i = 0; i < 8; ++i) tb[i] = i < b.ntasks ? b.t[i].tile_begin : 0x7fffffff;
   h.total_tiles = b.total_tiles; h.publish = b.publish != nullptr;
   h.tb1 = tb[1]; h.tb2 = tb[2]; h.tb3 = tb[3]; h.tb4 = tb[4]; h.tb5 = tb[5]; h.tb6 = tb[6]; h.tb7 = tb[7];
+  h.adam_blocks = b.adam_blocks;
+  h.side_blocks = b.rg.ring ? b.rg.blocks : 0;
+  h.flags = (b.rg.ring ? kHeadRing : 0) | (inl ? kHeadInl : 0) | (b.fuse_adam ? kHeadFuse : 0) |
+            (b.fuse_adam && b.adam.copy_src ? kHeadCopy : 0) | (b.adam.advance ? kHeadAdvance : 0);
+  h.state = b.fuse_adam ? b.adam.state : (b.rg.ring ? b.rg.state : nullptr);
   return h;
+}
+
+// a uniform word of the launch's StepState by a scalar load (no launch writes
+// a field another block of it reads, adam_common.h)
+__device__ __forceinline__ long long state_batch_counter(const StepState* st) {
+  return ((const __attribute__((address_space(4))) StepState*)(uintptr_t)st)->batch_counter;
 }
 
 // one workgroup's share of a launch: block `bid` of the batch (the kernel
@@ -266,24 +310,24 @@ struct SmallLds {
 // and with the fused optimizer its Adam (+ Polyak) on the prefetched p, m, v, t
 // (as epi_one's EPI_GRAD elements)
 struct FoldIn { float p, m, v, t; };
-__device__ __forceinline__ FoldIn fold_prefetch(const GemmBatch& batch, const float* g) {
+__device__ __forceinline__ FoldIn fold_prefetch(const EpiAdam& ea, const float* g) {
   FoldIn x{0.f, 0.f, 0.f, 0.f};
-  const long i = g - batch.adam.g;
-  x.p = batch.adam.p[i]; x.m = batch.adam.m[i]; x.v = batch.adam.v[i];
-  if (batch.adam.target) x.t = batch.adam.target[i];
+  const long i = g - ea.a.g;
+  x.p = ea.a.p[i]; x.m = ea.a.m[i]; x.v = ea.a.v[i];
+  if (ea.a.target) x.t = ea.a.target[i];
   return x;
 }
-__device__ __forceinline__ void fold_store(const GemmBatch& batch, const AdamConsts& ac, bool adam,
+__device__ __forceinline__ void fold_store(const EpiAdam& ea, const AdamConsts& ac, bool adam,
                                            float* g, float val, FoldIn x) {
   *g = val;
   if (!adam) return;
-  const long i = g - batch.adam.g;
+  const long i = g - ea.a.g;
   float p = x.p, m = x.m, v = x.v;
   adam1(ac, p, val, m, v);
-  (batch.adam.p_out ? batch.adam.p_out : batch.adam.p)[i] = p;
-  if (!batch.adam.preview) {
-    batch.adam.m[i] = m; batch.adam.v[i] = v;
-    if (ac.polyak) batch.adam.target[i] = polyak1(ac, x.t, p);
+  (ea.a.p_out ? ea.a.p_out : ea.a.p)[i] = p;
+  if (!ea.a.preview) {
+    ea.a.m[i] = m; ea.a.v[i] = v;
+    if (ac.polyak) ea.a.target[i] = polyak1(ac, x.t, p);
   }
 }
 
@@ -311,29 +355,23 @@ __device__ __forceinline__ floatx4 hd_mfma(const float* arow, const float (&hb)[
 // (GemmTask::C2; its own instance, as FOLDK, so the other launches keep
 // their registers and schedule)
 template <int NW, int GPW, bool FOLDK = false, bool HD2 = false>
-__device__ __forceinline__ void gemm_small_block(int bid, int total_tiles, int publish, int tb1,
-                                                 int tb2, int tb3, int tb4, int tb5, int tb6,
-                                                 int tb7, const GemmBatch& batch, float* red,
-                                                 const int* inl = nullptr) {
+__device__ __forceinline__ void gemm_small_block(int bid, const GemmHead& h, const GemmBatch& batch,
+                                                 float* red, const int* inl = nullptr) {
   constexpr int PER = 1024 / (64 * NW);   // epilogue elements per thread
+  const int total_tiles = h.total_tiles;
   GS_STAGE(0);
-  if (publish && bid == 0 && threadIdx.x == 0)
+  if (h.publish && bid == 0 && threadIdx.x == 0)
     publish_step_consts(batch.publish, batch.pub_beta1, batch.pub_beta2);
-  const int* rows = nullptr;   // direct drop-in gather: this step's index slot (host memory)
-  long long bc = 0;
-  if (inl) {   // the indices in the kernel arguments (gemm_small_kernel_inl)
-    bc = batch.rg.state->batch_counter;
-    rows = inl;
-  } else if (batch.rg.ring) {
-    bc = batch.rg.state->batch_counter;
-    rows = batch.rg.ring + (long)(bc % batch.rg.slots) * batch.rg.B;
-  }
-  if (bid >= total_tiles + batch.adam_blocks) {   // side blocks: the batch copy and the eps draws
+  if (bid >= total_tiles + h.adam_blocks) {   // side blocks: the batch copy and the eps draws
     // one wave per row: the row's index is one read of the host slot per
     // wave (every lane the same word), the row's float4s all in flight before
     // their stores; then the eps
     const RowGather& g = batch.rg;
-    const int sb = bid - total_tiles - batch.adam_blocks;
+    // this step's indices: the kernel arguments (gemm_small_kernel_inl) or the
+    // index slot (host memory); bc is also the Philox counter of the eps
+    const long long bc = state_batch_counter(h.state);
+    const int* rows = inl ? inl : g.ring + (long)(bc % g.slots) * g.B;
+    const int sb = bid - total_tiles - h.adam_blocks;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const long n4 = g.row_stride >> 2;
     const int nwv = g.blocks * NW;
@@ -372,8 +410,10 @@ __device__ __forceinline__ void gemm_small_block(int bid, int total_tiles, int p
       }
       return;
     }
-    const AdamConsts c = adam_consts(a.state, a.advance, a.lr, a.beta1, a.beta2, a.eps,
-                                     a.target, a.tau, a.period);
+    // (the StepState words through the header's pointer: they go out with
+    // the kernel-argument loads, not after them)
+    const AdamConsts c = adam_consts_finish(adam_state_request(h.state, h.flags & kHeadAdvance), a.lr,
+                                            a.beta1, a.beta2, a.eps, a.target, a.tau, a.period);
     const long stride = (long)batch.adam_blocks * 64 * NW;
     for (int sgi = 0; sgi < batch.nseg; ++sgi) {
       AdamArgs r = a;
@@ -387,11 +427,31 @@ __device__ __forceinline__ void gemm_small_block(int bid, int total_tiles, int p
     return;
   }
   int ti = 0;   // task of this block from the preloaded tile starts (no memory access)
-  ti = bid >= tb1 ? 1 : ti; ti = bid >= tb2 ? 2 : ti; ti = bid >= tb3 ? 3 : ti;
-  ti = bid >= tb4 ? 4 : ti; ti = bid >= tb5 ? 5 : ti; ti = bid >= tb6 ? 6 : ti;
-  ti = bid >= tb7 ? 7 : ti;
+  ti = bid >= h.tb1 ? 1 : ti; ti = bid >= h.tb2 ? 2 : ti; ti = bid >= h.tb3 ? 3 : ti;
+  ti = bid >= h.tb4 ? 4 : ti; ti = bid >= h.tb5 ? 5 : ti; ti = bid >= h.tb6 ? 6 : ti;
+  ti = bid >= h.tb7 ? 7 : ti;
   ti = __builtin_amdgcn_readfirstlane(ti);
+  // every address of the first scalar loads comes from the header: the task
+  // record and, in the index-slot form, batch_counter go out together
   GemmTask t = batch.t[ti];
+  const EpiAdam ea{(h.flags & kHeadFuse) != 0, (h.flags & kHeadAdvance) != 0, batch.adam};
+  // ... and with them the StepState words of adam_consts, which the epilogue
+  // needs after the reduction's barrier: they come back with the task record.
+  // (A launch without the fused optimizer reads the words, unused, from its
+  // own argument segment: no branch inside the group.  The asm statement
+  // below keeps the loads from sinking to their use below the barrier.)
+  AdamStateIn si = adam_state_request(
+      ea.fuse ? h.state : (const StepState*)(uintptr_t)__builtin_amdgcn_kernarg_segment_ptr(), ea.advance);
+  // direct drop-in gather: this step's indices, in the kernel arguments
+  // (gemm_small_kernel_inl: a tile block reads no StepState word) or in the
+  // index slot (host memory) that batch_counter names
+  const int* rows = nullptr;
+  if (inl) {
+    rows = inl;
+  } else if (h.flags & kHeadRing) {
+    const long long bc = state_batch_counter(h.state);
+    rows = batch.rg.ring + (long)(bc % batch.rg.slots) * batch.rg.B;
+  }
   int local = bid - t.tile_begin;
   int k_lo = 0, k_hi = t.K;
   if (t.ksplit > 1) {
@@ -406,6 +466,7 @@ __device__ __forceinline__ void gemm_small_block(int bid, int total_tiles, int p
   const int n0 = (local % t.tiles_n) * 32;
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // wave-uniform
+  asm volatile("" : "+s"(si.nsteps), "+s"(si.bc_t), "+s"(si.bc1), "+s"(si.sbc2));
   GS_STAGE(1);
   // the direct gather's row indices (host memory, the longest wait of the
   // launch): one read of the tile's 32 by wave 0, handed to the other waves
@@ -423,12 +484,12 @@ __device__ __forceinline__ void gemm_small_block(int bid, int total_tiles, int p
   for (int i = 0; i < PER; ++i) {
     const int e = threadIdx.x + i * 64 * NW;
     const int r = e >> 6, l = e & 63;
-    xin[i] = epi_prefetch(batch, t, m0 + (r & 3) + 8 * (r >> 2) + 4 * (l >> 5), n0 + (l & 31));
+    xin[i] = epi_prefetch(ea, t, m0 + (r & 3) + 8 * (r >> 2) + 4 * (l >> 5), n0 + (l & 31));
   }
   // GemmTask::fold (first column block): thread f < 32 finishes row m0 + f's
   // bias-column and width-1-layer sums, thread 32 (tile m0 = 0) the seed sum
   const bool fold = FOLDK && t.fold && n0 == 0;   // (workgroup-uniform)
-  const bool fold_adam = fold && batch.fuse_adam && !t.no_adam;
+  const bool fold_adam = fold && ea.fuse && !t.no_adam;
   floatx16 acc;
 #pragma unroll
   for (int r = 0; r < 16; ++r) acc[r] = 0.f;
@@ -469,8 +530,8 @@ __device__ __forceinline__ void gemm_small_block(int bid, int total_tiles, int p
   FoldIn fb{}, fw{};
   if (fold_adam && threadIdx.x < 33) {
     const int fm = min(m0 + (int)threadIdx.x, t.M - 1);
-    fb = fold_prefetch(batch, threadIdx.x < 32 ? t.bias_grad + fm : t.C2 + t.ldc2);
-    fw = fold_prefetch(batch, t.C2 + fm);
+    fb = fold_prefetch(ea, threadIdx.x < 32 ? t.bias_grad + fm : t.C2 + t.ldc2);
+    fw = fold_prefetch(ea, t.C2 + fm);
   }
 
   if (t.K2 > 0) {   // second product into the same accumulator (unsplit dX tasks only)
@@ -526,11 +587,8 @@ __device__ __forceinline__ void gemm_small_block(int bid, int total_tiles, int p
     }
     __syncthreads();
   }
-  AdamConsts ac{};
-  if (batch.fuse_adam)
-    ac = adam_consts(batch.adam.state, batch.adam.advance, batch.adam.lr, batch.adam.beta1,
-                     batch.adam.beta2, batch.adam.eps, batch.adam.target, batch.adam.tau,
-                     batch.adam.period);
+  AdamConsts ac{};   // from the StepState words and arguments the prologue loaded
+  if (ea.fuse) ac = adam_consts_finish(si, ea.a.lr, ea.a.beta1, ea.a.beta2, ea.a.eps, ea.a.target, ea.a.tau, ea.a.period);
   if constexpr (HD2) {
     if (hd) {   // the head backward, then its dX columns
       __syncthreads();   // (every wave's reads of the partial tiles are done: the LDS is reused)
@@ -572,8 +630,8 @@ __device__ __forceinline__ void gemm_small_block(int bid, int total_tiles, int p
           if (col < t.R && m < t.M) t.C2[(long)m * t.ldc2 + col] = mk > 0.f ? c[r] : 0.f;
         }
       }
-      if (batch.fuse_adam && !batch.adam.no_book && bid == 0 && threadIdx.x == 0)
-        step_bookkeeping(batch.adam.state, batch.adam.alpha, batch.adam.advance);
+      if (ea.fuse && !ea.a.no_book && bid == 0 && threadIdx.x == 0)
+        step_bookkeeping(const_cast<StepState*>(h.state), ea.a.alpha, ea.advance);
       return;
     }
   }
@@ -583,7 +641,7 @@ __device__ __forceinline__ void gemm_small_block(int bid, int total_tiles, int p
     const int r = e >> 6, l = e & 63;
     const int mt = (r & 3) + 8 * (r >> 2) + 4 * (l >> 5);
     const int nt = l & 31;
-    epi_one(batch, ac, t, m0 + mt, n0 + nt, vals[i], xin[i], lds_u, lds_v, mt, nt);
+    epi_one(ea, ac, t, m0 + mt, n0 + nt, vals[i], xin[i], lds_u, lds_v, mt, nt);
     if (t.epi == EPI_BIAS_RELU_DOT) {
       // the 32 lanes of a half-wave hold one row's 32 columns: fixed butterfly
       const int m = m0 + mt, n = n0 + nt;
@@ -595,24 +653,22 @@ __device__ __forceinline__ void gemm_small_block(int bid, int total_tiles, int p
   }
   if (fold && threadIdx.x < 32 && m0 + (int)threadIdx.x < t.M) {
     const int m = m0 + threadIdx.x;
-    fold_store(batch, ac, fold_adam, t.bias_grad + m, fsum_a, fb);
-    fold_store(batch, ac, fold_adam, t.C2 + m, fsum_b, fw);
+    fold_store(ea, ac, fold_adam, t.bias_grad + m, fsum_a, fb);
+    fold_store(ea, ac, fold_adam, t.C2 + m, fsum_b, fw);
   } else if (fold && threadIdx.x == 32 && m0 == 0) {
-    fold_store(batch, ac, fold_adam, t.C2 + t.ldc2, fsum_a, fb);
+    fold_store(ea, ac, fold_adam, t.C2 + t.ldc2, fsum_a, fb);
   }
-  if (batch.fuse_adam && !batch.adam.no_book && bid == 0 && threadIdx.x == 0)
-    step_bookkeeping(batch.adam.state, batch.adam.alpha, batch.adam.advance);
+  if (ea.fuse && !ea.a.no_book && bid == 0 && threadIdx.x == 0)
+    step_bookkeeping(const_cast<StepState*>(h.state), ea.a.alpha, ea.advance);
   GS_STAGE(4);
 }
 
 template <int NW, int GPW, bool FOLDK = false, bool HD2 = false>
 __global__ void __launch_bounds__(64 * NW)
-gemm_small_kernel(int total_tiles, int publish, int tb1, int tb2, int tb3, int tb4, int tb5, int tb6,
-                  int tb7, const GemmBatch batch) {
+gemm_small_kernel(OAC_HEAD_PARAMS, const GemmBatch batch) {
   static_assert(!HD2 || (NW >= 8 && SmallLds<NW, FOLDK>::N >= 32 * 65), "HD2: 8+ waves, dhead in LDS");
   __shared__ __attribute__((aligned(16))) float red[SmallLds<NW, FOLDK>::N];
-  gemm_small_block<NW, GPW, FOLDK, HD2>(blockIdx.x, total_tiles, publish, tb1, tb2, tb3, tb4, tb5,
-                                        tb6, tb7, batch, red);
+  gemm_small_block<NW, GPW, FOLDK, HD2>(blockIdx.x, OAC_HEAD_OF_PARAMS, batch, red);
 }
 
 // The direct drop-in layer-0 launch with the step's B <= 256 indices in the
@@ -626,25 +682,26 @@ struct InlineRows { int r[kInlineRows]; };
 // (each at its own alignment, in order): it mirrors gemm_small_kernel_inl's
 // parameter list, which must change with it.
 struct InlineKernArgs {
-  int total_tiles, publish, tb1, tb2, tb3, tb4, tb5, tb6, tb7;
+  int total_tiles, publish, tb1, tb2, tb3, tb4, tb5, tb6, tb7, adam_blocks, side_blocks, flags;
+  const StepState* state;
   GemmBatch batch;
   InlineRows ir;
 };
 constexpr size_t kInlineRowsOff = offsetof(InlineKernArgs, ir);
-static_assert(offsetof(InlineKernArgs, batch) % alignof(GemmBatch) == 0 &&
+static_assert(offsetof(InlineKernArgs, state) == 12 * sizeof(int) &&
+                  offsetof(InlineKernArgs, batch) == 14 * sizeof(int) &&   // (GemmHead's 14 dwords)
+                  offsetof(InlineKernArgs, batch) % alignof(GemmBatch) == 0 &&
                   kInlineRowsOff == offsetof(InlineKernArgs, batch) + sizeof(GemmBatch),
               "inline rows must follow the batch argument directly");
 template <int NW, int GPW>
 __global__ void __launch_bounds__(64 * NW)
-gemm_small_kernel_inl(int total_tiles, int publish, int tb1, int tb2, int tb3, int tb4, int tb5,
-                      int tb6, int tb7, const GemmBatch batch, const InlineRows ir) {
+gemm_small_kernel_inl(OAC_HEAD_PARAMS, const GemmBatch batch, const InlineRows ir) {
   __shared__ __attribute__((aligned(16))) float red[SmallLds<NW>::N];
   (void)ir;
   const __attribute__((address_space(4))) char* ka =
       (const __attribute__((address_space(4))) char*)__builtin_amdgcn_kernarg_segment_ptr();
   const int* rows = (const int*)(ka + kInlineRowsOff);
-  gemm_small_block<NW, GPW>(blockIdx.x, total_tiles, publish, tb1, tb2, tb3, tb4, tb5, tb6, tb7,
-                            batch, red, rows);
+  gemm_small_block<NW, GPW>(blockIdx.x, OAC_HEAD_OF_PARAMS, batch, red, rows);
 }
 
 // tile geometry shared with the plan builder
@@ -700,9 +757,12 @@ hipError_t gemm_small_launch(const GemmBatch& b0, hipStream_t s, BatchCache* bc 
     if (b.adam_blocks < 1 && b.nseg > 0) b.adam_blocks = 1;
   }
   const int grid = b.total_tiles + b.adam_blocks + (b.rg.ring ? b.rg.blocks : 0);
-  const GemmHead h = gemm_head(b);
   const bool inl = b.rg.inl && b.rg.ring && b.rg.B <= kInlineRows &&
                    ((nw == 16 && gpw == 4) || (nw == 8 && gpw == 5));
+  // the header names one StepState: the fused optimizer's and the row gather's must be the same
+  if (b.fuse_adam && b.rg.ring && b.adam.state != b.rg.state) return hipErrorInvalidValue;
+  if ((b.fuse_adam && !b.adam.state) || (b.rg.ring && !b.rg.state)) return hipErrorInvalidValue;
+  const GemmHead h = gemm_head(b, inl);
   bool has_fold = false, has_hd = false;
   for (int i = 0; i < b.ntasks; ++i) {
     has_fold = has_fold || b.t[i].fold;
@@ -726,11 +786,9 @@ hipError_t gemm_small_launch(const GemmBatch& b0, hipStream_t s, BatchCache* bc 
     }
     if (rmax > 8 * nw) return hipErrorInvalidValue;
     if (nw == 16 && gpw == 4)
-      OAC_LAUNCH((gemm_small_kernel<16, 4, false, true>), dim3(grid), dim3(64 * 16), 0, s, h.total_tiles,
-                 h.publish, h.tb1, h.tb2, h.tb3, h.tb4, h.tb5, h.tb6, h.tb7, b);
+      OAC_LAUNCH((gemm_small_kernel<16, 4, false, true>), dim3(grid), dim3(64 * 16), 0, s, OAC_HEAD_ARGS(h), b);
     else if (nw == 8 && gpw == 5)
-      OAC_LAUNCH((gemm_small_kernel<8, 5, false, true>), dim3(grid), dim3(64 * 8), 0, s, h.total_tiles,
-                 h.publish, h.tb1, h.tb2, h.tb3, h.tb4, h.tb5, h.tb6, h.tb7, b);
+      OAC_LAUNCH((gemm_small_kernel<8, 5, false, true>), dim3(grid), dim3(64 * 8), 0, s, OAC_HEAD_ARGS(h), b);
     else
       return hipErrorInvalidValue;
     return hipGetLastError();
@@ -739,18 +797,15 @@ hipError_t gemm_small_launch(const GemmBatch& b0, hipStream_t s, BatchCache* bc 
     InlineRows ir;
     std::memcpy(ir.r, b.rg.inl, sizeof(int) * b.rg.B);
     if (nw == 16)
-      OAC_LAUNCH((gemm_small_kernel_inl<16, 4>), dim3(grid), dim3(64 * 16), 0, s, h.total_tiles, h.publish,
-                 h.tb1, h.tb2, h.tb3, h.tb4, h.tb5, h.tb6, h.tb7, b, ir);
+      OAC_LAUNCH((gemm_small_kernel_inl<16, 4>), dim3(grid), dim3(64 * 16), 0, s, OAC_HEAD_ARGS(h), b, ir);
     else
-      OAC_LAUNCH((gemm_small_kernel_inl<8, 5>), dim3(grid), dim3(64 * 8), 0, s, h.total_tiles, h.publish,
-                 h.tb1, h.tb2, h.tb3, h.tb4, h.tb5, h.tb6, h.tb7, b, ir);
+      OAC_LAUNCH((gemm_small_kernel_inl<8, 5>), dim3(grid), dim3(64 * 8), 0, s, OAC_HEAD_ARGS(h), b, ir);
     return hipGetLastError();
   }
   if (has_fold) {   // the fold kernels: the default wave / k-group pairs only
 #define OAC_GSF(NW_, G_) \
     if (nw == NW_ && gpw == G_) { \
-      OAC_LAUNCH((gemm_small_kernel<NW_, G_, true>), dim3(grid), dim3(64 * NW_), 0, s, h.total_tiles, \
-                 h.publish, h.tb1, h.tb2, h.tb3, h.tb4, h.tb5, h.tb6, h.tb7, b); \
+      OAC_LAUNCH((gemm_small_kernel<NW_, G_, true>), dim3(grid), dim3(64 * NW_), 0, s, OAC_HEAD_ARGS(h), b); \
       return hipGetLastError(); }
     OAC_GSF(1, 5) OAC_GSF(2, 5) OAC_GSF(4, 5) OAC_GSF(8, 5) OAC_GSF(16, 4)
 #undef OAC_GSF
@@ -758,8 +813,7 @@ hipError_t gemm_small_launch(const GemmBatch& b0, hipStream_t s, BatchCache* bc 
   }
 #define OAC_GS(NW_, G_) \
   if (nw == NW_ && gpw == G_) { \
-    OAC_LAUNCH((gemm_small_kernel<NW_, G_>), dim3(grid), dim3(64 * NW_), 0, s, h.total_tiles, h.publish, \
-               h.tb1, h.tb2, h.tb3, h.tb4, h.tb5, h.tb6, h.tb7, b); \
+    OAC_LAUNCH((gemm_small_kernel<NW_, G_>), dim3(grid), dim3(64 * NW_), 0, s, OAC_HEAD_ARGS(h), b); \
     return hipGetLastError(); }
   OAC_GS(1, 5) OAC_GS(2, 5) OAC_GS(4, 5) OAC_GS(8, 5) OAC_GS(16, 4)
   OAC_GS(4, 3) OAC_GS(4, 4) OAC_GS(4, 6) OAC_GS(4, 8)

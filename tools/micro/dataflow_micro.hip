@@ -161,8 +161,7 @@ dataflow_kernel(const Stages sg, const TileDep* __restrict__ deps, int nst,
       wait_dep<FENCE>(ctr, d);
       asm volatile("" ::"v"(warm));
       if (threadIdx.x == 0 && vb == w0 && st > 0) my[2 * st] = wall_clock64();
-      gemm_small_block<NW, GPW>(vb, h.total_tiles, h.publish, h.tb1, h.tb2, h.tb3, h.tb4, h.tb5,
-                                h.tb6, h.tb7, bs[st], red);
+      gemm_small_block<NW, GPW>(vb, h, bs[st], red);
       signal_dep<FENCE>(ctr, d);
     }
     if (threadIdx.x == 0) my[2 * st + 1] = wall_clock64();

@@ -95,8 +95,7 @@ chain_kernel(const GemmBatch* bs, const GemmHead* hs, int nst, unsigned* bar) {
     const GemmHead h = hs[st];
     const int grid = h.total_tiles + bs[st].adam_blocks;
     for (int vb = blockIdx.x; vb < grid; vb += gridDim.x) {
-      gemm_small_block<NW, GPW>(vb, h.total_tiles, h.publish, h.tb1, h.tb2, h.tb3, h.tb4, h.tb5,
-                                h.tb6, h.tb7, bs[st], red);
+      gemm_small_block<NW, GPW>(vb, h, bs[st], red);
       __syncthreads();
     }
     if (st + 1 < nst) grid_sync<HIER>(bar, st + 1);
