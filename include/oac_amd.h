@@ -104,6 +104,29 @@ typedef struct oac_sac_config {
    * and the target_policy only); the policy is trained by the sweep,
    * oac_sac_policy_opt_* below.  0 in a zero-initialised config */
   int global_opt;
+  /* OAC_KIND_GAUSS (q_out == 2) / OAC_KIND_PARTICLE_UB (2 <= q_out <= 16):
+   * share_layers=False, the reference trainers' default -- q_out separate
+   * one-output critics (gaussian_trainer.py:100-112: q and std; particle_trainer.py:
+   * 105-114: K particles), each with its own optimizer, instead of one critic
+   * with q_out outputs.  Needs n_hidden == 1, world_size == 1, global_opt == 0
+   * and hidden % 4 == 0.  The critics are stored stacked, as one critic block
+   * of hidden width q_out * hidden whose last layer is block-diagonal:
+   * q_fc0_w [q_out * hidden, obs_dim + act_dim], q_fc0_b [q_out * hidden],
+   * q_last_w [q_out * hidden] (critic k's last_fc.weight = slice k), q_last_b
+   * [q_out]; critic k's tensors are slice k of each, contiguous.  n_critics =
+   * q_out, q2_base = -1, q_fc1_* = -1, targets_total = q_size.  PARTICLE_UB:
+   * critic i's loss is MSE(sorted_qs[i], targets[i]) (not divided by q_out)
+   * and only critic i is stepped on it, so dL/dq_i[r] is nonzero only on the
+   * rows where critic i holds sorted rank i.  freeze_q_bias then freezes every
+   * critic's last bias (PARTICLE_UB) or the std critic's alone (GAUSS).  Such a
+   * handle rejects OAC_STEP_USE_GRAPH, oac_sac_step_phase and
+   * oac_sac_set_allreduce.  0 in a zero-initialised config */
+  int unshared;
+  /* GAUSS with unshared: the std critic's learning rate (std_optimizer,
+   * gaussian_trainer.py:108-110); the q critic's is qf_lr.  A double, as
+   * qf_lr (torch's Adam divides the double lr by the bias correction).
+   * Unused otherwise */
+  double std_lr;
 } oac_sac_config;
 
 /* Flat parameter arena layout (float offsets; every tensor 16-byte aligned).

@@ -40,6 +40,17 @@
 // kernel (det_seed_head_backward_kernel) carries both policy losses from the
 // post-step critic's hidden activations to the policy heads' gradients.
 // Launches beyond gather / counts: 2 + 2 + 4 = 8 (two layers: 18).
+//
+// share_layers=False (c.unshared, one hidden layer only: the reference
+// trainers' default, gaussian_trainer.py:100-112 / particle_trainer.py:105-114):
+// K separate one-output critics, each with its own optimizer -- q | std for
+// GAUSS, one per particle for PARTICLE_UB -- stored as ONE stacked critic block
+// of hidden width K H whose last layer is block-diagonal.  The chain above
+// carries over with every critic product K H wide (q_hidden); the RowHeads take
+// the segment width (RowHead::seg), the particle loss keeps only the rows
+// where a critic holds its own rank (ParticleTargetArgs::rank_only, loss scale
+// 1), and the last layer's gradient with the whole block's per-critic Adam +
+// Polyak is one row launch after the layer-0 dW (seg_last_update_kernel): 9.
 #include <cstring>
 
 #include "../../include/oac_amd.h"
@@ -82,6 +93,8 @@ void det_layout_workspace(SacPlan& p) {
   for (int id : {G_DH2Q, G_DH1Q, G_PN, G_H1N, G_H2N, G_PN3, G_H1N3, G_H2N3, G_DH2N, G_DH1N,
                  G_DH2N3, G_DH1N3, G_DH2P, G_DH1P, G_DH2TP, G_DH1TP})
     set(id, B, H);
+  if (c.unshared)   // the stacked critic block's hidden layer: K H wide
+    for (int id : {G_P, G_H1Q, G_PT, G_H1T, G_DH1Q, G_PN, G_H1N, G_PN3, G_H1N3}) set(id, B, q_hidden(p));
   for (int id : {G_DA, G_DA3}) set(id, B, Da);
   for (int id : {G_DHEAD, G_DHEAD3}) set(id, B, 2 * Da);
   if (c.global_opt) set(G_OPT, 1, 2 * kPolicyOptMaxBlocks + 64);
@@ -135,7 +148,9 @@ static int dphase0(SacPlan& p, int flags, hipStream_t s) {
     std::memset(&a, 0, sizeof(a));
     a.ld_wa = Dq; a.det = 1;
     a.B = B; a.H = H; a.Da = Da;
-    a.col_chunks = std::max(1, (H + (B >= 1024 ? 127 : 63)) / (B >= 1024 ? 128 : 64));
+    const int Hq = q_hidden(p);   // (the target critic's columns: the stacked block's when unshared)
+    if (c.unshared) a.Hq = Hq;
+    a.col_chunks = std::max(1, (Hq + (B >= 1024 ? 127 : 63)) / (B >= 1024 ? 128 : 64));
     // (global_opt: the policy(obs) segment is not run; the other two move up)
     const int k0 = go ? 2 : 0, k1 = go ? 0 : 1, k2 = go ? 1 : 2;
     HeadSeg& s0 = a.seg[k0];   // policy(obs) -> a~ (post-step critic, phase 2)
@@ -170,13 +185,16 @@ static int dphase1(SacPlan& p, int flags, hipStream_t s, bool fused) {
   }
   // the target critic's K-output last layer runs inside the targets kernel
   // (row_heads, rows.hip): one launch fewer on the chain
-  const RowHead th{p.W(sh ? G_H1T : G_H2T), tq + L.q_last_w, tq + L.q_last_b, p.W(OAC_WS_TQ1), H};
+  // (unshared: the K critics stacked, hidden width K H, block-diagonal last
+  // layer -- RowHead::seg = H)
+  const int Hq = q_hidden(p), seg = c.unshared ? H : 0;
+  const RowHead th{p.W(sh ? G_H1T : G_H2T), tq + L.q_last_w, tq + L.q_last_b, p.W(OAC_WS_TQ1), Hq, seg};
   // one hidden layer: Q(obs, a)'s last layer too, and its backward into the
   // hidden layer, dh1q = [h1q > 0] (dq . W_last) (float4 columns: H % 4 == 0,
   // checked when the plan is created)
   RowHead qh;
   std::memset(&qh, 0, sizeof(qh));
-  if (sh) qh = RowHead{p.W(G_H1Q), q + L.q_last_w, q + L.q_last_b, p.W(OAC_WS_Q1), H};
+  if (sh) qh = RowHead{p.W(G_H1Q), q + L.q_last_w, q + L.q_last_b, p.W(OAC_WS_Q1), Hq, seg};
   float* dh_out = sh ? p.W(G_DH1Q) : nullptr;
   const float* counts = (flags & OAC_STEP_COUNTS) ? p.W(OAC_WS_COUNTS) : nullptr;
   if (c.kind == OAC_KIND_GAUSS) {
@@ -198,9 +216,42 @@ static int dphase1(SacPlan& p, int flags, hipStream_t s, bool fused) {
     a.dq = p.W(G_DQ); a.sqe = p.W(OAC_WS_SQE1); a.y = p.W(OAC_WS_Y); a.counts = counts; a.th = th;
     a.qh = qh; a.dh2 = dh_out;
     a.loss_scale = 1.f / (float)K;                       // qf_loss /= num_particles
+    if (c.unshared) {   // particle_trainer.py:271-278: loss i alone, for critic i alone
+      a.loss_scale = 1.f;
+      a.rank_only = 1;
+    }
     a.soft_prob = c.std_soft_update ? c.std_soft_prob : -1.f;
     a.rescale_spread = c.rescale_spread;
     RUN_ROW(p, s, launch_particle_targets(a, s));
+  }
+  if (c.unshared) {
+    // Layer 0's dW as one product of width K H; the block-diagonal last
+    // layer's gradient is no GEMM, and the critics step at their own learning
+    // rates (GAUSS: qf_lr | std_lr), which one epilogue Adam cannot apply: one
+    // more launch forms the last-layer gradient and steps the whole block
+    // (Adam + Polyak + the critic Adam's bookkeeping), after the split-K slabs,
+    // if any, are reduced into the gradient arena.
+    {
+      GemmBatch gb{};
+      add(gb, critic_l0_dw(p, G_DH1Q));
+      if (run_gemm(p, gb, s)) return 1;
+    }
+    if (p.S_q > 1) {
+      AdamArgs r = critic_adam(p, 1, nullptr);
+      r.n = (long)L.q_last_w;   // layer 0: [fc0.weight | fc0.bias]
+      if (run_adam(p, r, s)) return 1;
+    }
+    SegLastArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.dq = p.W(G_DQ); a.h = p.W(G_H1Q);
+    a.B = B; a.K = K; a.Hs = H; a.Dq = c.obs_dim + c.act_dim;
+    a.off_b0 = (long)L.q_fc0_b; a.off_w = (long)L.q_last_w; a.off_b = (long)L.q_last_b;
+    a.n0 = (long)L.q_last_w;
+    if (c.freeze_q_bias) a.freeze_mask = c.kind == OAC_KIND_GAUSS ? 2u : (1u << K) - 1u;
+    if (c.kind == OAC_KIND_GAUSS) { a.lr1_mask = 2u; a.lr1 = c.std_lr; }
+    a.adam = critic_adam(p, -1, nullptr);   // (the arena's gradients, S = 1; world_size 1: gscale 1)
+    RUN_ROW(p, s, launch_seg_last_update(a, s));
+    return 0;
   }
   if (sh) {   // both weight gradients in one launch
     GemmBatch gb{};
@@ -260,7 +311,8 @@ static int dphase2(SacPlan& p, hipStream_t s, bool fused) {
     {
       DetSeedHeadBwdArgs a;
       std::memset(&a, 0, sizeof(a));
-      a.hn = RowHead{p.W(G_H1N), q + L.q_last_w, q + L.q_last_b, p.W(OAC_WS_QN1), H};
+      a.hn = RowHead{p.W(G_H1N), q + L.q_last_w, q + L.q_last_b, p.W(OAC_WS_QN1), q_hidden(p),
+                     c.unshared ? H : 0};
       a.h1n1 = p.W(G_H1N3);
       a.wa = q + L.q_fc0_w + c.obs_dim; a.ld_wa = c.obs_dim + Da;
       a.act[0] = p.W(OAC_WS_ACT1); a.dhead[0] = p.W(G_DHEAD);
@@ -380,7 +432,8 @@ int det_run_step(SacPlan& p, int flags, hipStream_t s, int, int) {
   const bool fused = can_fuse_adam(p);
   if (dphase0(p, flags, s)) return 1;
   if (dphase1(p, flags, s, fused)) return 1;
-  if (!fused && run_adam(p, critic_adam(p, 0, nullptr), s)) return 1;
+  // (unshared: phase 1's last launch has stepped the critic block)
+  if (!fused && !p.c.unshared && run_adam(p, critic_adam(p, 0, nullptr), s)) return 1;
   if (dphase2(p, s, fused)) return 1;
   if (!fused && run_adam(p, p.c.global_opt ? tpol_adam(p) : policy_adam(p, 0, nullptr), s)) return 1;
   return 0;

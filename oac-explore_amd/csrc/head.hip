@@ -49,7 +49,9 @@ constexpr int kRows = 16;
 // per wave of step 3 (2: <= 16 pairs per workgroup; 4: a whole 256-column
 // hidden layer of both nets in one workgroup, the large-batch form, no
 // recomputed heads); KS = k-steps of 4 action dims held per pair (Da <= 4*KS)
-template <int NT, int KP, int KS>
+// WIDE: the critics' hidden layer is HeadArgs::Hq wide instead of H (a form of
+// its own: the other launches keep their registers and schedule)
+template <int NT, int KP, int KS, bool WIDE = false>
 __global__ void __launch_bounds__(64 * kHeadWaves) policy_head_kernel(const HeadArgs a) {
   // one LDS array: reduction scratch, then the head tile and the actions
   constexpr int kRed = kHeadWaves * 4 * 4 * 64;   // waves x col tiles x regs x lanes
@@ -115,7 +117,8 @@ __global__ void __launch_bounds__(64 * kHeadWaves) policy_head_kernel(const Head
   head_loads(wave);   // chunk past the end: clamped, its MFMAs skipped
 
   // ---- 0. prefetch what steps 2-3 read besides the head GEMM operands
-  const int cols = (H + a.col_chunks - 1) / a.col_chunks;
+  const int Hq = WIDE ? a.Hq : H;   // the critics' hidden width
+  const int cols = (Hq + a.col_chunks - 1) / a.col_chunks;
   const int n_lo = chunk * cols;
   const int tiles = (cols + 15) / 16;
   const int pairs = sg.n_nets * tiles;
@@ -136,10 +139,10 @@ __global__ void __launch_bounds__(64 * kHeadWaves) policy_head_kernel(const Head
     const bool pv = pi < pairs;
     const int net = pv ? pi / tiles : 0;
     const int n = n_lo + (pi % tiles) * 16 + l16;
-    const bool nv = pv && n < H && n < n_lo + cols;
+    const bool nv = pv && n < Hq && n < n_lo + cols;
     const float* wrow = pv ? sg.wa[net] + (long)(nv ? n : 0) * a.ld_wa : wh;
     const float* prow = pv ? sg.pre[net] + (nv ? n : 0) : wh;
-    const long pld = pv ? (long)H : 0;
+    const long pld = pv ? (long)Hq : 0;
 #pragma unroll
     for (int st = 0; st < KS; ++st) bw_pf[q][st] = wrow[pv ? min(4 * st + g4, Da - 1) : 0];
 #pragma unroll
@@ -227,7 +230,7 @@ __global__ void __launch_bounds__(64 * kHeadWaves) policy_head_kernel(const Head
     if (pi >= pairs) break;
     const int net = pi / tiles;
     const int n = n_lo + (pi % tiles) * 16 + l16;
-    const bool nv = n < H && n < n_lo + cols;
+    const bool nv = n < Hq && n < n_lo + cols;
     floatx4 c = floatx4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int st = 0; st < KS; ++st)
@@ -240,20 +243,25 @@ __global__ void __launch_bounds__(64 * kHeadWaves) policy_head_kernel(const Head
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int m = m0 + 4 * g4 + r;
-      if (m < B && nv) sg.h1[net][(long)m * H + n] = fmaxf(c[r] + pre_pf[q][r], 0.f);
+      if (m < B && nv) sg.h1[net][(long)m * Hq + n] = fmaxf(c[r] + pre_pf[q][r], 0.f);
     }
   }
   STAGE(4);
 }
 
+template <int KP, int KS, bool WIDE>
+static void launch_head_w(const HeadArgs& a, dim3 grid, dim3 block, hipStream_t s) {
+  switch ((2 * a.Da + 15) / 16) {
+    case 1: OAC_LAUNCH((policy_head_kernel<1, KP, KS, WIDE>), grid, block, 0, s, a); break;
+    case 2: OAC_LAUNCH((policy_head_kernel<2, KP, KS, WIDE>), grid, block, 0, s, a); break;
+    case 3: OAC_LAUNCH((policy_head_kernel<3, KP, KS, WIDE>), grid, block, 0, s, a); break;
+    default: OAC_LAUNCH((policy_head_kernel<4, KP, KS, WIDE>), grid, block, 0, s, a); break;
+  }
+}
 template <int KP, int KS>
 static void launch_head_nt(const HeadArgs& a, dim3 grid, dim3 block, hipStream_t s) {
-  switch ((2 * a.Da + 15) / 16) {
-    case 1: OAC_LAUNCH((policy_head_kernel<1, KP, KS>), grid, block, 0, s, a); break;
-    case 2: OAC_LAUNCH((policy_head_kernel<2, KP, KS>), grid, block, 0, s, a); break;
-    case 3: OAC_LAUNCH((policy_head_kernel<3, KP, KS>), grid, block, 0, s, a); break;
-    default: OAC_LAUNCH((policy_head_kernel<4, KP, KS>), grid, block, 0, s, a); break;
-  }
+  if (a.Hq > 0) launch_head_w<KP, KS, true>(a, grid, block, s);
+  else launch_head_w<KP, KS, false>(a, grid, block, s);
 }
 
 hipError_t launch_policy_head(const HeadArgs& a, int nseg, hipStream_t s) {
@@ -263,7 +271,7 @@ hipError_t launch_policy_head(const HeadArgs& a, int nseg, hipStream_t s) {
   for (int i = 0; i < nseg; ++i)
     if (a.seg[i].n_nets < 0 || a.seg[i].n_nets > 2) return hipErrorInvalidValue;
   // every (net, 16-column tile) of a workgroup's chunk is prefetched: <= 4 per wave
-  const int cols = (a.H + a.col_chunks - 1) / a.col_chunks;
+  const int cols = ((a.Hq ? a.Hq : a.H) + a.col_chunks - 1) / a.col_chunks;
   int pairs = 0;
   for (int i = 0; i < nseg; ++i) pairs = std::max(pairs, a.seg[i].n_nets * ((cols + 15) / 16));
   if (pairs > 4 * kHeadWaves) return hipErrorInvalidValue;

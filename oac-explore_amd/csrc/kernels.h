@@ -69,6 +69,11 @@ struct HeadArgs {
   // non-null: segment 0's row blocks also write sum_rows (logp + te) of their
   // 16 rows (rows in order) to logp_part[row block] (data-parallel alpha)
   float* logp_part; float target_entropy;
+  // > 0: the critics' hidden layer (pre / h1 / wa rows) is Hq wide, not H (a
+  // stacked critic block, det_plan.hip unshared): a kernel form of its own, so
+  // the launches with Hq == 0 run the code they always ran.  Last, so every
+  // other field keeps its place in the kernel arguments.
+  int Hq;
 };
 hipError_t launch_policy_head(const HeadArgs& a, int nseg, hipStream_t s);
 
@@ -217,10 +222,15 @@ hipError_t launch_priority_sample(const int* counts, long size, const double* u,
 // A critic's K-output last layer evaluated inside a row kernel instead of a
 // separate GEMM launch (det_plan.hip): out[r, k] = b[k] + sum_j h[r, j] W[k, j]
 // for the kernel's 16-row block (h null: the outputs were stored by a GEMM)
+// seg > 0 (share_layers=False: K one-output critics stacked into one block of
+// hidden width H = K seg): the last layer is block-diagonal, W is the [H]
+// vector of the K critics' last_fc.weight rows and
+// out[r, k] = b[k] + sum_{k seg <= j < (k + 1) seg} h[r, j] W[j]
 struct RowHead {
   const float* h; const float* w; const float* b;   // h [B, H], W [K, H], b [K]
   float* out;                                        // [B, K] (workspace view, diagnostics)
   int H;
+  int seg;                                           // 0: dense W [K, H]
 };
 
 struct ParticleTargetArgs {
@@ -243,6 +253,10 @@ struct ParticleTargetArgs {
   float loss_scale;                     // 1/K: qf_loss /= num_particles (:269)
   float soft_prob;                      // std_soft_update_prob (:222-231), < 0: off
   float rescale_spread;                 // rescale_targets_around_mean (:254-262), <= 0: off
+  // share_layers=False (particle_trainer.py:271-278): critic i is stepped on
+  // loss i = MSE(sorted_qs[i], targets[i]) alone, so dq[r, k] keeps its value
+  // only where critic k holds sorted rank k in row r and is 0 elsewhere
+  int rank_only;
 };
 struct ParticleMinArgs {
   const float* qn; int B, K;            // [B, K] Q(obs, a~) with the post-step critic
@@ -364,6 +378,27 @@ struct DdpgHeadBwdArgs {
   int B, H, Da;
 };
 hipError_t launch_ddpg_head_backward(const DdpgHeadBwdArgs& a, hipStream_t s);
+
+// share_layers=False (det_plan.hip, unshared): the stacked critics' last-layer
+// gradient and the whole critic block's optimizer step in one launch.
+//   dw[n] = sum_r dq[r, n / Hs] h[r, n],  db[k] = sum_r dq[r, k]  (rows in a
+//   fixed order; db[k] = 0 for a frozen bias), stored to the gradient arena,
+// then Adam (+ Polyak) on the last layer with the gradient just formed and on
+// layer 0 (elements [0, a.n0) of the group, gradients from a.adam.g: the dW
+// launch before this one), each element at its critic's learning rate:
+// critic k = (i / (Hs Dq)) in fc0.weight, ((i - off_b0) / Hs) in fc0.bias, n / Hs
+// in the last layer; lr1 where bit k of lr1_mask is set, adam.lr elsewhere.
+// Block 0 does the critic Adam's bookkeeping (StepState::t_snapshot).
+struct SegLastArgs {
+  const float* dq; const float* h;      // [B, K], [B, K Hs]
+  int B, K, Hs, Dq;
+  long off_b0, off_w, off_b;            // fc0.bias, last_fc.weight, last_fc.bias in the group
+  long n0;                              // layer 0's elements: [0, n0) = fc0.weight | fc0.bias
+  unsigned freeze_mask;                 // bit k: critic k's last bias has no gradient
+  unsigned lr1_mask; double lr1;        // critics stepped at lr1 instead of adam.lr
+  AdamArgs adam;                        // the critic group (p, g, m, v, target, state, ...)
+};
+hipError_t launch_seg_last_update(const SegLastArgs& a, hipStream_t s);
 
 // global_opt (utils/core.py:64-137 optimize_policy): the sweep iteration's
 // obs-only gather, out[r, off + c] = replay[idx[r], off + c] for c < Do

@@ -45,6 +45,26 @@ static void compute_layout(const oac_sac_config& c, oac_sac_layout& L) {
   L.pol_head_b = o; o = al4(o + 2 * Da);
   L.pol_size = o;
   int64_t q = 0;
+  if (c.unshared) {
+    // share_layers=False: Q one-output critics of one hidden layer, stacked into
+    // one block of hidden width Q H with a block-diagonal last layer -- fc0.weight
+    // [Q H, Do + Da], fc0.bias [Q H], last_fc.weight [Q H] (critic k's [1, H] row
+    // = slice k), last_fc.bias [Q]; critic k's tensors are slice k of each
+    // (H % 4 == 0: every slice of the first three 16-byte aligned)
+    L.q_fc0_w = q; q = al4(q + Q * H * (Do + Da));
+    L.q_fc0_b = q; q = al4(q + Q * H);
+    L.q_fc1_w = L.q_fc1_b = -1;
+    L.q_last_w = q; q = al4(q + Q * H);
+    L.q_last_b = q; q = al4(q + Q);
+    L.q_size = q;
+    L.n_critics = Q;
+    L.tpol_base = L.pol_size;
+    L.q1_base = 2 * L.pol_size;
+    L.q2_base = -1;
+    L.params_total = L.q1_base + L.q_size;
+    L.targets_total = L.q_size;
+    return;
+  }
   L.q_fc0_w = q; q = al4(q + H * (Do + Da));
   L.q_fc0_b = q; q = al4(q + H);
   L.q_fc1_w = two ? q : -1; if (two) q = al4(q + H * H);
@@ -201,7 +221,7 @@ static int validate(const oac_sac_config* c) {
               c->kind, names[c->kind], OAC_KIND_GAUSS, OAC_KIND_PARTICLE_UB);
     return 1;
   }
-  if (c->n_hidden == 1 && (c->hidden & 3)) {
+  if (c->n_hidden == 1 && (c->hidden & 3) && !c->unshared) {   // (unshared: its own message below)
     set_error("n_hidden = 1: hidden must be a multiple of 4 (the row kernels read the hidden "
               "activations as float4 columns), got %d", c->hidden);
     return 1;
@@ -216,6 +236,43 @@ static int validate(const oac_sac_config* c) {
               "implemented for GAUSS (kind %d) and PARTICLE_UB (kind %d), single process",
               c->kind, names[c->kind], c->world_size, OAC_KIND_GAUSS, OAC_KIND_PARTICLE_UB);
     return 1;
+  }
+  if (c->unshared != 0 && c->unshared != 1) {
+    set_error("unshared must be 0 or 1, got %d (kind %d)", c->unshared, c->kind);
+    return 1;
+  }
+  if (c->unshared) {   // share_layers=False: q_out stacked one-output critics (det_plan.hip)
+    static const char* const names[] = {"SAC", "PARTICLE", "GAUSS", "PARTICLE_UB", "DDPG"};
+    const char* nm = names[c->kind];
+    if (!has_target_policy(c->kind)) {
+      set_error("unshared: kind %d (%s) is not supported; separate critics are implemented for "
+                "GAUSS (kind %d, q_out == 2) and PARTICLE_UB (kind %d, 2 <= q_out <= 16)",
+                c->kind, nm, OAC_KIND_GAUSS, OAC_KIND_PARTICLE_UB);
+      return 1;
+    }
+    if (c->n_hidden != 1) {
+      set_error("unshared (kind %d, %s): n_hidden must be 1 (one hidden layer), got %d", c->kind, nm,
+                c->n_hidden);
+      return 1;
+    }
+    if (c->world_size != 1) {
+      set_error("unshared (kind %d, %s): world_size must be 1 (single process), got %d", c->kind, nm,
+                c->world_size);
+      return 1;
+    }
+    if (c->global_opt) {
+      set_error("unshared (kind %d, %s): global_opt must be 0, got %d", c->kind, nm, c->global_opt);
+      return 1;
+    }
+    if (c->hidden & 3) {
+      set_error("unshared (kind %d, %s): hidden must be a multiple of 4, got %d", c->kind, nm, c->hidden);
+      return 1;
+    }
+    if (c->kind == OAC_KIND_GAUSS && !(c->std_lr > 0.0)) {
+      set_error("unshared (kind %d, %s): std_lr must be > 0 (the std critic's learning rate), got %g",
+                c->kind, nm, c->std_lr);
+      return 1;
+    }
   }
   if (c->obs_dim < 1 || c->act_dim < 1 || c->act_dim > 32 || c->hidden < 1 || c->batch < 1) {
     set_error("bad dims obs=%d act=%d hidden=%d batch=%d", c->obs_dim, c->act_dim, c->hidden, c->batch);
@@ -243,7 +300,8 @@ static void plan_splits(SacPlan& p) {
   const int nq = (c.kind == OAC_KIND_SAC) ? 2 : 1;
   p.sp_q1 = choose_split(c.batch, nq * (tiles(H, H + 1) + tiles(c.q_out, H + 1)), p.cfg);
   p.sp_ql = p.sp_q1;
-  p.sp_q0 = choose_split(c.batch, nq * tiles(H, Dq + 1), p.cfg);
+  const int Hq = q_hidden(p);   // (unshared: the stacked critic block's width)
+  p.sp_q0 = choose_split(c.batch, nq * tiles(Hq, Dq + 1), p.cfg);
   p.sp_ph = choose_split(c.batch, tiles(2 * Da, H + 1), p.cfg);
   p.sp_p1 = choose_split(c.batch, tiles(H, H + 1), p.cfg);
   p.sp_p0 = choose_split(c.batch, tiles(H, Do + 1), p.cfg);
@@ -251,7 +309,7 @@ static void plan_splits(SacPlan& p) {
     auto t64 = [](int M, int Nx) { return ((M + 63) / 64) * ((Nx + 63) / 64); };
     p.sp_q1 = choose_split_pipe(c.batch, nq * (t64(H, H) + t64(c.q_out, H)));
     p.sp_ql = p.sp_q1;
-    p.sp_q0 = choose_split_pipe(c.batch, nq * t64(H, Dq));
+    p.sp_q0 = choose_split_pipe(c.batch, nq * t64(Hq, Dq));
     // the particle trainer's K-output last-layer dW rides in the layer-0 dW
     // launch (particle_plan.hip, hidden % 4 == 0): the same chunks as the
     // layer-0 dW, so neither is that launch's tail (configs[4]: 16 splits of
@@ -350,6 +408,11 @@ int oac_sac_step_n(oac_sac* h, int flags, int n_steps, void* stream) {
   }
   if (p.c.global_opt && (flags & OAC_STEP_USE_GRAPH)) {
     set_error("global_opt (kind %d): OAC_STEP_USE_GRAPH is not supported, issue the step's launches "
+              "directly", p.c.kind);
+    return 1;
+  }
+  if (p.c.unshared && (flags & OAC_STEP_USE_GRAPH)) {
+    set_error("unshared (kind %d): OAC_STEP_USE_GRAPH is not supported, issue the step's launches "
               "directly", p.c.kind);
     return 1;
   }
@@ -550,6 +613,10 @@ int oac_sac_step_phase(oac_sac* h, int phase, int flags, void* stream) {
     set_error("oac_sac_step_phase: a global_opt handle (kind %d) is single-process", h->plan.c.kind);
     return 1;
   }
+  if (h->plan.c.unshared) {
+    set_error("oac_sac_step_phase: an unshared handle (kind %d) is single-process", h->plan.c.kind);
+    return 1;
+  }
   return step_phase(h->plan, phase, flags, reinterpret_cast<hipStream_t>(stream));
 }
 
@@ -559,6 +626,10 @@ int oac_sac_set_allreduce(oac_sac* h, oac_allreduce_fn fn, void* ctx, int flags)
   if (no_dp_step(p, "oac_sac_set_allreduce")) return 1;
   if (p.c.global_opt) {
     set_error("oac_sac_set_allreduce: a global_opt handle (kind %d) is single-process", p.c.kind);
+    return 1;
+  }
+  if (p.c.unshared) {
+    set_error("oac_sac_set_allreduce: an unshared handle (kind %d) is single-process", p.c.kind);
     return 1;
   }
   if (fn && (flags & OAC_DP_OVERLAP) && !p.side) {

@@ -284,6 +284,10 @@ __device__ __forceinline__ void load_row16(const float* src, int K, float (&v)[k
 // GEMM launch that otherwise sits between the hidden layer and this kernel.
 constexpr int kRowBlock = 16;
 static bool head_ok(const RowHead& h) { return !h.h || (h.w && h.b && h.out && h.H >= 1); }
+// a block-diagonal head (RowHead::seg): K segments of a multiple of 4 hidden units
+static bool seg_ok(const RowHead& h, int K) {
+  return !h.h || !h.seg || (h.seg > 0 && (h.seg & 3) == 0 && h.H == K * h.seg);
+}
 typedef float floatx4 __attribute__((ext_vector_type(4)));
 typedef float f4a __attribute__((ext_vector_type(4), aligned(4)));
 
@@ -292,12 +296,21 @@ struct RowHeadLds {
   float out[kRowBlock][kMaxHeads];
 };
 
+// SEG (RowHead::seg != 0, a compile-time form of its own so the dense form
+// keeps its registers: the kernels that never see a block-diagonal head
+// instantiate the dense one alone): lane k's B operand is W[n] inside segment
+// k of the [H] vector -- the hidden units [blo, bhi) -- and 0 elsewhere, not
+// row k of a dense W; seg % 4 == 0, so a lane's four k values of a load lie in
+// one segment.  Same MFMA order, reduction order and width paths.
+template <bool SEG = false>
 __device__ __forceinline__ void row_heads(const RowHead& hd, int K, int B, int r0, RowHeadLds& sh) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int l16 = lane & 15, g4 = lane >> 4;
   const float* arow = hd.h + (long)min(r0 + l16, B - 1) * hd.H;
-  const float* brow = hd.w + (long)min(l16, K - 1) * hd.H;
-  const bool bv = l16 < K;
+  const float* brow = hd.w + (SEG ? 0 : (long)min(l16, K - 1) * hd.H);
+  const int blo = SEG ? l16 * hd.seg : 0;
+  const int bhi = (SEG && l16 < K) ? blo + hd.seg : 0;
+  const bool bdense = l16 < K;
   floatx4 acc = floatx4{0.f, 0.f, 0.f, 0.f};
   const int chunks = (hd.H + 15) >> 4;
   if ((hd.H & 15) == 0 && hd.H <= 256) {
@@ -305,18 +318,20 @@ __device__ __forceinline__ void row_heads(const RowHead& hd, int K, int B, int r
     // branch between the loads and the MFMAs made them wait for every load
     constexpr int kQ = 4;
     f4a xa[kQ], xb[kQ];
+    bool bv[kQ];
 #pragma unroll
     for (int q = 0; q < kQ; ++q) {
       const int kb = 16 * min(wave + 4 * q, chunks - 1) + 4 * g4;
       xa[q] = *reinterpret_cast<const f4a*>(arow + kb);
       xb[q] = *reinterpret_cast<const f4a*>(brow + kb);
+      bv[q] = SEG ? (kb >= blo && kb < bhi) : bdense;
     }
 #pragma unroll
     for (int q = 0; q < kQ; ++q)
       if (wave + 4 * q < chunks) {
 #pragma unroll
         for (int e = 0; e < 4; ++e)
-          acc = __builtin_amdgcn_mfma_f32_16x16x4f32(xa[q][e], bv ? xb[q][e] : 0.f, acc, 0, 0, 0);
+          acc = __builtin_amdgcn_mfma_f32_16x16x4f32(xa[q][e], bv[q] ? xb[q][e] : 0.f, acc, 0, 0, 0);
       }
   } else {
     // up to 4 chunks per wave in flight (all of them for H <= 256): the loads
@@ -325,9 +340,11 @@ __device__ __forceinline__ void row_heads(const RowHead& hd, int K, int B, int r
 #pragma unroll 1
     for (int c0 = wave; c0 < chunks; c0 += 4 * kQ) {
       float xa[kQ][4], xb[kQ][4];
+      bool bv[kQ];
 #pragma unroll
       for (int q = 0; q < kQ; ++q) {
         const int kb = 16 * (c0 + 4 * q) + 4 * g4;
+        bv[q] = SEG ? (kb >= blo && kb < bhi) : bdense;
         if (kb + 3 < hd.H) {
           const f4a a = *reinterpret_cast<const f4a*>(arow + kb);
           const f4a b = *reinterpret_cast<const f4a*>(brow + kb);
@@ -345,7 +362,7 @@ __device__ __forceinline__ void row_heads(const RowHead& hd, int K, int B, int r
       for (int q = 0; q < kQ; ++q)
 #pragma unroll
         for (int e = 0; e < 4; ++e)
-          acc = __builtin_amdgcn_mfma_f32_16x16x4f32(xa[q][e], bv ? xb[q][e] : 0.f, acc, 0, 0, 0);
+          acc = __builtin_amdgcn_mfma_f32_16x16x4f32(xa[q][e], bv[q] ? xb[q][e] : 0.f, acc, 0, 0, 0);
     }
   }
 #pragma unroll
@@ -367,15 +384,20 @@ __device__ __forceinline__ void row_heads(const RowHead& hd, int K, int B, int r
 // targets kernel's target critic and critic): all loads of both issued
 // before the first MFMA, one LDS round.  Same per-head MFMA order as
 // row_heads.  H % 16 == 0 and H <= 256 (one k-batch per wave).
+template <bool SEG = false>
 __device__ __forceinline__ void row_heads2(const RowHead& h0, const RowHead& h1, int K, int B, int r0,
                                            RowHeadLds& s0, RowHeadLds& s1) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int l16 = lane & 15, g4 = lane >> 4;
   const int H = h0.H, chunks = H >> 4;
-  const long ra = (long)min(r0 + l16, B - 1) * H, rb = (long)min(l16, K - 1) * H;
-  const bool bv = l16 < K;
+  // (SEG: h0.seg == h1.seg, the critic and its target; the lane's B operand as in row_heads)
+  const long ra = (long)min(r0 + l16, B - 1) * H, rb = SEG ? 0 : (long)min(l16, K - 1) * H;
+  const int blo = SEG ? l16 * h0.seg : 0;
+  const int bhi = (SEG && l16 < K) ? blo + h0.seg : 0;
+  const bool bdense = l16 < K;
   constexpr int kQ = 4;
   f4a x0[kQ], w0[kQ], x1[kQ], w1[kQ];
+  bool bv[kQ];
 #pragma unroll
   for (int q = 0; q < kQ; ++q) {   // unpredicated (clamped chunk): no branch before the MFMAs
     const int kb = 16 * min(wave + 4 * q, chunks - 1) + 4 * g4;
@@ -383,6 +405,7 @@ __device__ __forceinline__ void row_heads2(const RowHead& h0, const RowHead& h1,
     w0[q] = *reinterpret_cast<const f4a*>(h0.w + rb + kb);
     x1[q] = *reinterpret_cast<const f4a*>(h1.h + ra + kb);
     w1[q] = *reinterpret_cast<const f4a*>(h1.w + rb + kb);
+    bv[q] = SEG ? (kb >= blo && kb < bhi) : bdense;
   }
   floatx4 acc0 = floatx4{0.f, 0.f, 0.f, 0.f}, acc1 = acc0;
 #pragma unroll
@@ -390,10 +413,10 @@ __device__ __forceinline__ void row_heads2(const RowHead& h0, const RowHead& h1,
     if (wave + 4 * q < chunks) {
 #pragma unroll
       for (int e = 0; e < 4; ++e)
-        acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(x0[q][e], bv ? w0[q][e] : 0.f, acc0, 0, 0, 0);
+        acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(x0[q][e], bv[q] ? w0[q][e] : 0.f, acc0, 0, 0, 0);
 #pragma unroll
       for (int e = 0; e < 4; ++e)
-        acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(x1[q][e], bv ? w1[q][e] : 0.f, acc1, 0, 0, 0);
+        acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(x1[q][e], bv[q] ? w1[q][e] : 0.f, acc1, 0, 0, 0);
     }
 #pragma unroll
   for (int r = 0; r < 4; ++r) { s0.red[wave][r][lane] = acc0[r]; s1.red[wave][r][lane] = acc1[r]; }
@@ -413,21 +436,34 @@ __device__ __forceinline__ void row_heads2(const RowHead& h0, const RowHead& h1,
   }
 }
 
+// a head of either form (workgroup-uniform): the targets kernels and the
+// depth-1 seed kernel, which a block-diagonal last layer reaches
+__device__ __forceinline__ void row_heads_any(const RowHead& hd, int K, int B, int r0, RowHeadLds& sh) {
+  if (hd.seg) row_heads<true>(hd, K, B, r0, sh);
+  else row_heads<false>(hd, K, B, r0, sh);
+}
+__device__ __forceinline__ void row_heads2_any(const RowHead& h0, const RowHead& h1, int K, int B,
+                                               int r0, RowHeadLds& s0, RowHeadLds& s1) {
+  if (h0.seg) row_heads2<true>(h0, h1, K, B, r0, s0, s1);
+  else row_heads2<false>(h0, h1, K, B, r0, s0, s1);
+}
+
 __device__ __forceinline__ void particle_targets_rows(const ParticleTargetArgs& p, RowHeadLds& hs,
                                                       RowHeadLds& qs,
                                                       float (&sdq)[kRowBlock][kMaxHeads]) {
   const int r0 = blockIdx.x * kRowBlock, r = r0 + threadIdx.x;
   const int K = p.K;
-  if (p.th.h && p.qh.h && p.th.H == p.qh.H && (p.th.H & 15) == 0 && p.th.H <= 256) {
-    row_heads2(p.th, p.qh, K, p.B, r0, hs, qs);   // both heads, loads issued together
+  if (p.th.h && p.qh.h && p.th.H == p.qh.H && p.th.seg == p.qh.seg && (p.th.H & 15) == 0 &&
+      p.th.H <= 256) {
+    row_heads2_any(p.th, p.qh, K, p.B, r0, hs, qs);   // both heads, loads issued together
     __syncthreads();
   } else {
     if (p.th.h) {
-      row_heads(p.th, K, p.B, r0, hs);
+      row_heads_any(p.th, K, p.B, r0, hs);
       __syncthreads();
     }
     if (p.qh.h) {   // the critic's own last layer on (obs, a) (particle_trainer_oac.py:185-191)
-      row_heads(p.qh, K, p.B, r0, qs);
+      row_heads_any(p.qh, K, p.B, r0, qs);
       __syncthreads();
     }
   }
@@ -531,7 +567,8 @@ __device__ __forceinline__ void particle_targets_rows(const ParticleTargetArgs& 
   for (int i = 0; i < kMaxHeads; ++i) {
     if (i < K) {
       const float d = q[i] - y[i];
-      const float g = __fmul_rn(g2 * d, invB);
+      // (rank_only: loss i reaches critic i alone, through the rows where it holds rank i)
+      const float g = (p.rank_only && qi[i] != i) ? 0.f : __fmul_rn(g2 * d, invB);
       p.y[(long)r * K + i] = y[i];
       p.sqe[(long)r * K + i] = d * d;
       p.dq[(long)r * K + qi[i]] = g;
@@ -544,6 +581,26 @@ __device__ __forceinline__ void particle_targets_rows(const ParticleTargetArgs& 
 // per 256 threads (n4 <= 64), four passes over a 16-row block
 __device__ __forceinline__ int rows_per_pass(int n4) { return 256 / n4; }
 
+// The 16 rows' backward through a block-diagonal last layer (RowHead::seg) by
+// the whole block: dh[r, n] = [h[r, n] > 0] g[r][n / seg] w[n], g = the rows'
+// output gradients in LDS ([kRowBlock][ldg]).  float4 columns: seg % 4 == 0,
+// so a float4 lies inside one segment.
+__device__ __forceinline__ void seg_last_backward(const RowHead& hd, const float* g, int ldg, int r0,
+                                                  int B, float* dh) {
+  const int H = hd.H, n4 = H >> 2;
+  for (int e = threadIdx.x; e < kRowBlock * n4; e += 256) {
+    const int rr = e / n4, c = 4 * (e - rr * n4), m = r0 + rr;
+    if (m >= B) continue;
+    const float4 h = *reinterpret_cast<const float4*>(hd.h + (long)m * H + c);
+    const float4 w = *reinterpret_cast<const float4*>(hd.w + c);
+    const float gk = g[rr * ldg + c / hd.seg];
+    float4 o;
+    o.x = h.x > 0.f ? gk * w.x : 0.f; o.y = h.y > 0.f ? gk * w.y : 0.f;
+    o.z = h.z > 0.f ? gk * w.z : 0.f; o.w = h.w > 0.f ? gk * w.w : 0.f;
+    *reinterpret_cast<float4*>(dh + (long)m * H + c) = o;
+  }
+}
+
 // the targets kernel's row logic, then (p.dh2) the 16 rows' backward into
 // the last hidden layer by the whole block
 __global__ void __launch_bounds__(256) particle_targets_kernel(ParticleTargetArgs p) {
@@ -555,7 +612,7 @@ __global__ void __launch_bounds__(256) particle_targets_kernel(ParticleTargetArg
   // a thread's 4 elements share one float4 column c of the K weight rows, so
   // those and the 4 hidden-row float4s are requested before the heads (the
   // dh2 pass then starts on registers, not on a round trip after the rows)
-  const bool pre = p.dh2 && n4 <= 64 && n4 * kRowBlock <= 1024 && K <= kMaxHeads;
+  const bool pre = p.dh2 && n4 <= 64 && n4 * kRowBlock <= 1024 && K <= kMaxHeads && !p.qh.seg;
   float4 hpf[4], wpf[kMaxHeads];
   if (pre) {
     const int c = 4 * (threadIdx.x % n4), rr0 = threadIdx.x / n4, rstep = 256 / n4;
@@ -593,6 +650,10 @@ __global__ void __launch_bounds__(256) particle_targets_kernel(ParticleTargetArg
     return;
   }
   if (pre) return;
+  if (p.qh.seg) {   // block-diagonal last layer: dh[r, n] = [h > 0] dq[r, n / seg] w[n]
+    seg_last_backward(p.qh, &sdq[0][0], kMaxHeads, r0, p.B, p.dh2);
+    return;
+  }
   for (int e = threadIdx.x; e < kRowBlock * n4; e += 256) {
     const int rr = e / n4, c = 4 * (e - rr * n4), m = r0 + rr;
     if (m >= p.B) continue;
@@ -725,6 +786,7 @@ __global__ void __launch_bounds__(256) particle_min_kernel(ParticleMinArgs p) {
 
 hipError_t launch_particle_targets(const ParticleTargetArgs& a, hipStream_t s) {
   if (a.K > kMaxHeads || !head_ok(a.th) || !head_ok(a.qh)) return hipErrorInvalidValue;
+  if (!seg_ok(a.th, a.K) || !seg_ok(a.qh, a.K)) return hipErrorInvalidValue;
   if (a.dh2 && (!a.qh.h || (a.qh.H & 3))) return hipErrorInvalidValue;
   OAC_LAUNCH(particle_targets_kernel, dim3((a.B + kRowBlock - 1) / kRowBlock), dim3(256), 0, s, a);
   return hipGetLastError();
@@ -753,16 +815,17 @@ hipError_t launch_particle_min(const ParticleMinArgs& a, hipStream_t s) {
 __device__ __forceinline__ void gauss_targets_rows(const GaussTargetArgs& p, RowHeadLds& hs,
                                                    RowHeadLds& qs, float (&sdq)[kRowBlock][2]) {
   const int r0 = blockIdx.x * kRowBlock, r = r0 + threadIdx.x;
-  if (p.th.h && p.qh.h && p.th.H == p.qh.H && (p.th.H & 15) == 0 && p.th.H <= 256) {
-    row_heads2(p.th, p.qh, 2, p.B, r0, hs, qs);   // both heads, loads issued together
+  if (p.th.h && p.qh.h && p.th.H == p.qh.H && p.th.seg == p.qh.seg && (p.th.H & 15) == 0 &&
+      p.th.H <= 256) {
+    row_heads2_any(p.th, p.qh, 2, p.B, r0, hs, qs);   // both heads, loads issued together
     __syncthreads();
   } else {
     if (p.th.h) {
-      row_heads(p.th, 2, p.B, r0, hs);
+      row_heads_any(p.th, 2, p.B, r0, hs);
       __syncthreads();
     }
     if (p.qh.h) {   // the critic's own last layer on (obs, a)
-      row_heads(p.qh, 2, p.B, r0, qs);
+      row_heads_any(p.qh, 2, p.B, r0, qs);
       __syncthreads();
     }
   }
@@ -802,6 +865,10 @@ __global__ void __launch_bounds__(256) gauss_targets_kernel(GaussTargetArgs p) {
   if (!p.dh2) return;
   __syncthreads();
   const int r0 = blockIdx.x * kRowBlock, H = p.qh.H, n4 = H >> 2;
+  if (p.qh.seg) {   // the q and std critics stacked: a block-diagonal last layer
+    seg_last_backward(p.qh, &sdq[0][0], 2, r0, p.B, p.dh2);
+    return;
+  }
   for (int e = threadIdx.x; e < kRowBlock * n4; e += 256) {
     const int rr = e / n4, c = 4 * (e - rr * n4), m = r0 + rr;
     if (m >= p.B) continue;
@@ -915,7 +982,7 @@ __global__ void __launch_bounds__(256) det_seed_head_backward_kernel(DetSeedHead
   const int K = p.K, H = p.hn.H, Da = p.Da, B = p.B;
   const float g0 = -(1.f / (float)B);
   if (seg == 0) {
-    row_heads(p.hn, K, B, r0, hs);   // (-> QN1)
+    row_heads_any(p.hn, K, B, r0, hs);   // (-> QN1)
     __syncthreads();
     if (threadIdx.x < kRowBlock) {
       const int t = threadIdx.x;
@@ -960,7 +1027,11 @@ __global__ void __launch_bounds__(256) det_seed_head_backward_kernel(DetSeedHead
     for (int i = l; i < nc; i += 16) {
       const int n = c0 + i;
       float a = 0.f;
-      for (int k = 0; k < K; ++k) a = fmaf(sg[row][k], p.hn.w[(long)k * H + n], a);
+      if (p.hn.seg) {   // block-diagonal last layer: unit n belongs to critic n / seg
+        a = sg[row][n / p.hn.seg] * p.hn.w[n];
+      } else {
+        for (int k = 0; k < K; ++k) a = fmaf(sg[row][k], p.hn.w[(long)k * H + n], a);
+      }
       sdh[row][i] = h1[n] > 0.f ? a : 0.f;
     }
     __syncthreads();
@@ -989,6 +1060,86 @@ __global__ void __launch_bounds__(256) det_seed_head_backward_kernel(DetSeedHead
     dh[jl + 16] = __fmul_rn(acc1, __fsub_rn(1.f, __fmul_rn(a, a)));
     dh[Da + jl + 16] = 0.f;
   }
+}
+
+// --------------------------------------------------------------------------
+// share_layers=False (SegLastArgs): the stacked critics' last-layer gradient
+// and the critic block's optimizer step, each critic at its own learning rate
+// (gaussian_trainer.py:103-110 q_optimizer / std_optimizer; particle_trainer.py:
+// 112-114 one optimizer per particle).  Workgroups [0, nbw): 64 columns of
+// last_fc.weight each -- four row phases per column (rows p, p + 4, ... in
+// order), summed in phase order -- then Adam (+ Polyak) on those columns;
+// workgroup nbw: the K biases (16 row phases each, likewise); the rest: Adam
+// (+ Polyak) over layer 0 from the gradient arena.  A frozen bias takes a zero
+// gradient: Adam leaves it and its moments unchanged, Polyak still applies.
+// --------------------------------------------------------------------------
+constexpr int kSegCols = 64;
+__global__ void __launch_bounds__(256) seg_last_update_kernel(SegLastArgs p) {
+  __shared__ float part[4][kSegCols];
+  __shared__ float bpart[16][kMaxHeads];
+  const AdamArgs& a = p.adam;
+  const int K = p.K, H = p.K * p.Hs, B = p.B, t = threadIdx.x;
+  const int nbw = (H + kSegCols - 1) / kSegCols;
+  const int b = blockIdx.x;
+  const AdamConsts c0 = adam_consts(a.state, 0, a.lr, a.beta1, a.beta2, a.eps, a.target, a.tau, a.period);
+  const AdamConsts c1 = adam_consts(a.state, 0, p.lr1, a.beta1, a.beta2, a.eps, a.target, a.tau, a.period);
+  if (b == 0 && t == 0) step_bookkeeping_lead(a.state, nullptr, 0);   // (t_snapshot: read by no block here)
+  if (b < nbw) {
+    const int col = t & (kSegCols - 1), ph = t >> 6;
+    const int n = b * kSegCols + col, nc = min(n, H - 1), k = nc / p.Hs;
+    float s = 0.f;
+    for (int r = ph; r < B; r += 4) s = fmaf(p.dq[(long)r * K + k], p.h[(long)r * H + nc], s);
+    part[ph][col] = s;
+    __syncthreads();
+    if (t < kSegCols && n < H) {
+      const float g = ((part[0][t] + part[1][t]) + part[2][t]) + part[3][t];
+      const long i = p.off_w + n;
+      a.g[i] = g;
+      adam_elem((p.lr1_mask >> k) & 1u ? c1 : c0, a, i, g);
+    }
+    return;
+  }
+  if (b == nbw) {
+    const int k = t & 15, ph = t >> 4;
+    float s = 0.f;
+    if (k < K)
+      for (int r = ph; r < B; r += 16) s += p.dq[(long)r * K + k];
+    bpart[ph][k] = s;
+    __syncthreads();
+    if (t < K) {
+      float g = bpart[0][t];
+#pragma unroll
+      for (int q = 1; q < 16; ++q) g += bpart[q][t];
+      if ((p.freeze_mask >> t) & 1u) g = 0.f;
+      const long i = p.off_b + t;
+      a.g[i] = g;
+      adam_elem((p.lr1_mask >> t) & 1u ? c1 : c0, a, i, g);
+    }
+    return;
+  }
+  const long stride = (long)(gridDim.x - nbw - 1) * 256;
+  const long per_w = (long)p.Hs * p.Dq;
+  for (long i = (long)(b - nbw - 1) * 256 + t; i < p.n0; i += stride) {
+    const int k = (int)(i < p.off_b0 ? i / per_w : (i - p.off_b0) / p.Hs);
+    adam_elem((p.lr1_mask >> k) & 1u ? c1 : c0, a, i, a.g[i]);
+  }
+}
+
+hipError_t launch_seg_last_update(const SegLastArgs& a, hipStream_t s) {
+  const long H = (long)a.K * a.Hs;
+  if (!a.dq || !a.h || a.B < 1 || a.K < 1 || a.K > kMaxHeads || a.Hs < 1 || a.Dq < 1 ||
+      !a.adam.p || !a.adam.g || !a.adam.m || !a.adam.v || !a.adam.state)
+    return hipErrorInvalidValue;
+  // layer 0 = [fc0.weight | fc0.bias] at the head of the group, no padding
+  // between or after them; gradients already reduced into the arena
+  if (a.off_b0 != H * a.Dq || a.n0 != a.off_b0 + H || a.off_w < a.n0 || a.off_b < a.off_w + H ||
+      a.adam.S > 1 || a.adam.gslab != a.adam.g || a.adam.gscale != 1.f)
+    return hipErrorInvalidValue;
+  const int nbw = (int)((H + kSegCols - 1) / kSegCols);
+  const long want = (a.n0 + 255) / 256;
+  const int nflat = (int)(want < 1024 ? want : 1024);
+  OAC_LAUNCH(seg_last_update_kernel, dim3(nbw + 1 + nflat), dim3(256), 0, s, a);
+  return hipGetLastError();
 }
 
 // --------------------------------------------------------------------------
@@ -1087,6 +1238,7 @@ hipError_t launch_ddpg_head_backward(const DdpgHeadBwdArgs& a, hipStream_t s) {
 
 hipError_t launch_gauss_targets(const GaussTargetArgs& a, hipStream_t s) {
   if (!head_ok(a.th) || !head_ok(a.qh)) return hipErrorInvalidValue;
+  if (!seg_ok(a.th, 2) || !seg_ok(a.qh, 2)) return hipErrorInvalidValue;
   if (a.dh2 && (!a.qh.h || (a.qh.H & 3))) return hipErrorInvalidValue;
   OAC_LAUNCH(gauss_targets_kernel, dim3((a.B + kRowBlock - 1) / kRowBlock), dim3(256), 0, s, a);
   return hipGetLastError();
@@ -1104,7 +1256,7 @@ hipError_t launch_particle_ub_seed(const ParticleUbSeedArgs& a, hipStream_t s) {
 hipError_t launch_det_seed_head_backward(const DetSeedHeadBwdArgs& a, hipStream_t s) {
   if (!a.hn.h || !head_ok(a.hn) || !a.h1n1 || !a.wa || !a.ub || a.B < 1 || a.K < 1 ||
       a.K > kMaxHeads || (a.gauss && a.K != 2) || a.Da < 1 || a.Da > 32 ||
-      a.delta_index < 0 || a.delta_index >= kMaxHeads)
+      a.delta_index < 0 || a.delta_index >= kMaxHeads || !seg_ok(a.hn, a.K))
     return hipErrorInvalidValue;
   for (int g = 0; g < 2; ++g)
     if (!a.act[g] || !a.dhead[g]) return hipErrorInvalidValue;

@@ -65,7 +65,13 @@ inline float* grad_q(SacPlan& p) {
   return p.S_q > 1 ? p.W(WS_GSLAB_Q) : p.b.grads + p.L.q1_base;
 }
 inline float* grad_p(SacPlan& p) { return p.S_p > 1 ? p.W(WS_GSLAB_P) : p.b.grads; }
-inline long q_group(const SacPlan& p) { return (long)(p.L.n_critics * p.L.q_size); }
+// (unshared: the K critics are ONE stacked block of q_size floats)
+inline long q_group(const SacPlan& p) {
+  return (long)((p.c.unshared ? 1 : p.L.n_critics) * p.L.q_size);
+}
+// width of the critic block's hidden layer: the policy's, or (unshared: q_out
+// one-output critics stacked, block-diagonal last layer) q_out times it
+inline int q_hidden(const SacPlan& p) { return p.c.unshared ? p.c.q_out * p.c.hidden : p.c.hidden; }
 // the policy Adam group: everything in front of the critic block (the policy,
 // plus the target_policy for GAUSS)
 inline long p_group(const SacPlan& p) { return (long)p.L.q1_base; }
@@ -310,7 +316,7 @@ inline GemmTask pol_l1(SacPlan& p, const float* pol, int h1, int h2) {
 inline GemmTask critic_l0_rank(SacPlan& p, const float* q, const float* x, const float* u, long ldu,
                                int pre, int h1) {
   const oac_sac_config& c = p.c;
-  const int H = c.hidden, Do = c.obs_dim, Da = c.act_dim, Dq = Do + Da;
+  const int H = q_hidden(p), Do = c.obs_dim, Da = c.act_dim, Dq = Do + Da;
   GemmTask t = t_fwd(x, c.row_stride, c.batch, Do, q + p.L.q_fc0_w, Dq, H, p.W(pre), H,
                      EPI_BIAS_RANK_RELU, q + p.L.q_fc0_b);
   t.U = u; t.ldu = ldu; t.V = q + p.L.q_fc0_w + Do; t.ldv = Dq; t.R = Da;
@@ -321,8 +327,8 @@ inline GemmTask critic_l0_rank(SacPlan& p, const float* q, const float* x, const
 // adds the next actions' columns)
 inline GemmTask target_proj(SacPlan& p, const float* tq, const float* x, int pre) {
   const oac_sac_config& c = p.c;
-  return t_fwd(x, c.row_stride, c.batch, c.obs_dim, tq + p.L.q_fc0_w, c.obs_dim + c.act_dim, c.hidden,
-               p.W(pre), c.hidden, EPI_BIAS, tq + p.L.q_fc0_b);
+  return t_fwd(x, c.row_stride, c.batch, c.obs_dim, tq + p.L.q_fc0_w, c.obs_dim + c.act_dim, q_hidden(p),
+               p.W(pre), q_hidden(p), EPI_BIAS, tq + p.L.q_fc0_b);
 }
 // plain critic layer 1: h2 = relu(h1 W1^T + b1)
 inline GemmTask critic_l1(SacPlan& p, const float* q, int h1, int h2) {
@@ -392,7 +398,7 @@ inline GemmTask critic_l1_dx(SacPlan& p, int dh2, int dh1, int h1) {
 inline GemmTask critic_l0_dw(SacPlan& p, int dh1) {   // input = [obs | act] contiguous in the row
   const oac_sac_config& c = p.c;
   float* gq = grad_q(p);
-  return t_dw(p.W(dh1), c.hidden, c.hidden, c.batch, p.X() + c.off_obs, c.row_stride,
+  return t_dw(p.W(dh1), q_hidden(p), q_hidden(p), c.batch, p.X() + c.off_obs, c.row_stride,
               c.obs_dim + c.act_dim, gq + p.L.q_fc0_w, gq + p.L.q_fc0_b, q_group(p), p.sp_q0);
 }
 // Width-1 critic (SAC, DDPG): the backward into its last hidden layer, dh2 =

@@ -2,9 +2,11 @@
 
 Drop-in replacements for the reference's hot-path interfaces:
   SACTrainer                         trainer/trainer.py
-  ParticleTrainer                    trainer/particle_trainer.py (p-oac recipes, share_layers)
+  ParticleTrainer                    trainer/particle_trainer.py (p-oac recipes; share_layers,
+                                     or separate critics at one hidden layer)
   ParticleTrainerOAC                 trainer/particle_trainer_oac.py (share_layers)
-  GaussianTrainer                    trainer/gaussian_trainer.py (g-oac, share_layers)
+  GaussianTrainer                    trainer/gaussian_trainer.py (g-oac; share_layers, or
+                                     separate q / std critics at one hidden layer)
   DDPGTrainer                        trainer/ddpg_trainer.py (--alg ddpg)
   get_optimistic_exploration_action  optimistic_exploration.py
   ReplayBuffer, ReplayBufferCount    replay_buffer.py

@@ -64,8 +64,7 @@ def set_tuning_spec(spec):
 WS_OPTIONAL = ("h1p", "h2p")
 
 
-class SacConfig(ctypes.Structure):
-    _fields_ = [
+_SAC_CONFIG_FIELDS = [
         ("kind", ctypes.c_int), ("obs_dim", ctypes.c_int), ("act_dim", ctypes.c_int),
         ("hidden", ctypes.c_int), ("q_out", ctypes.c_int), ("batch", ctypes.c_int),
         ("discount", ctypes.c_float), ("reward_scale", ctypes.c_float), ("tau", ctypes.c_float),
@@ -81,7 +80,46 @@ class SacConfig(ctypes.Structure):
         ("mean_update", ctypes.c_int), ("delta_index", ctypes.c_int),
         ("rescale_spread", ctypes.c_float), ("freeze_q_bias", ctypes.c_int),
         ("n_hidden", ctypes.c_int), ("global_opt", ctypes.c_int),
-    ]
+]
+# oac_sac_config's fields after global_opt (include/oac_amd.h): share_layers=False
+_SAC_CONFIG_TAIL = [("unshared", ctypes.c_int), ("std_lr", ctypes.c_double)]
+
+
+class _SacConfigC(ctypes.Structure):
+    """The whole C struct: its size and the tail fields' offsets."""
+    _fields_ = _SAC_CONFIG_FIELDS + _SAC_CONFIG_TAIL
+
+
+def _tail_field(name, ctype):
+    off = getattr(_SacConfigC, name).offset
+
+    def get(self):
+        return ctype.from_buffer(self._buf, off).value
+
+    def put(self, value):
+        ctype.from_buffer(self._buf, off).value = value
+    return property(get, put)
+
+
+class SacConfig(ctypes.Structure):
+    """oac_sac_config.  ``_fields_`` declares the struct up to ``global_opt``,
+    the last field callers written before ``unshared`` / ``std_lr`` know (an
+    existing test pins it as the declaration's last entry); every instance is
+    backed by a zeroed buffer of the WHOLE C struct's size, so the library reads
+    an initialised tail, and the tail fields are attributes like the others."""
+    _fields_ = _SAC_CONFIG_FIELDS
+
+    def __new__(cls, *args, **kwargs):
+        buf = bytearray(ctypes.sizeof(_SacConfigC))
+        self = cls.from_buffer(buf)
+        self._buf = buf
+        return self
+
+
+for _n, _t in _SAC_CONFIG_TAIL:
+    setattr(SacConfig, _n, _tail_field(_n, _t))
+assert all(getattr(SacConfig, n).offset == getattr(_SacConfigC, n).offset
+           for n, _ in _SAC_CONFIG_FIELDS)
 
 
 class SacLayout(ctypes.Structure):

@@ -134,6 +134,11 @@ class _DataParallel:
             raise NotImplementedError(
                 "the data-parallel trainers do not implement global_opt (the policy sweep, "
                 "optimize_policies, is single-process); unsupported: ['global_opt']")
+        if isinstance(self, (ParticleTrainer, GaussianTrainer)) and not kwargs.get("share_layers"):
+            raise NotImplementedError(
+                "the data-parallel trainers do not implement share_layers=False (separate "
+                "critics, each with its own optimizer, are single-process); unsupported: "
+                "['share_layers']")
         if not dist.is_initialized():
             raise RuntimeError("DataParallelSACTrainer needs torch.distributed initialised")
         self.pg = process_group

@@ -38,19 +38,20 @@ class GaussianTrainer(_TargetPolicyTrainer):
                  std_soft_update_prob=0., train_bias=True, use_target_policy=False,
                  rescale_targets_around_mean=False,
                  device=None, seed=0, use_graph=False, gemm_cfg=-1):
-        unsupported = dict(share_layers=not share_layers, deterministic=not deterministic,
-                           ensemble=ensemble)
+        unsupported = dict(deterministic=not deterministic, ensemble=ensemble)
         bad = [k for k, v in unsupported.items() if v]
         if bad:
             raise NotImplementedError(
-                "oac_amd.GaussianTrainer implements the g-oac recipe configuration "
-                "(share_layers=True, deterministic policy, counts / std_soft_update / "
-                f"mean_update / use_target_policy, global_opt, no ensemble); unsupported: {bad}")
+                "oac_amd.GaussianTrainer implements the g-oac recipe configurations "
+                "(share_layers=True, or separate q / std critics of one hidden layer; "
+                "deterministic policy, counts / std_soft_update / mean_update / "
+                f"use_target_policy, global_opt, no ensemble); unsupported: {bad}")
         assert not counts or not std_soft_update   # gaussian_trainer.py:88
         self._common_init(device, soft_target_tau, target_update_period, deterministic,
                           discount, reward_scale, policy_lr, qf_lr, use_graph, seed, gemm_cfg)
         self.train_bias = train_bias
         self.std_lr = std_lr
+        self.unshared = not share_layers
         # gaussian_trainer.py:65-86
         self.action_space = action_space
         self.q_min, self.q_max, self.delta = q_min, q_max, delta
@@ -70,20 +71,38 @@ class GaussianTrainer(_TargetPolicyTrainer):
         # producer call order of the reference constructor: SACTrainer's policy
         # and four critics (unused), the shared-layer critic and its target,
         # then target_policy (gaussian_trainer.py:51-63, 91-99, 146)
+        if self.unshared:
+            self._reject_unshared_options()
         ref_pol = policy_producer()
         for _ in range(4):
             q_producer()
-        qb = np.array([mean, np.log(std)])
-        ref_q = q_producer(bias=qb, positive=[False, True], train_bias=train_bias)
-        ref_qt = q_producer(bias=qb, positive=[False, True], train_bias=train_bias)
+        if self.unshared:
+            # gaussian_trainer.py:100-112: q (always with a trained bias) and its
+            # target, then std (exp'd output; train_bias freezes its last bias
+            # alone) and its target, each pair built independently
+            ref_q = [q_producer(bias=mean)]
+            ref_qt = [q_producer(bias=mean)]
+            ref_q.append(q_producer(bias=np.log(std), positive=True, train_bias=train_bias))
+            ref_qt.append(q_producer(bias=np.log(std), positive=True, train_bias=train_bias))
+        else:
+            qb = np.array([mean, np.log(std)])
+            ref_q = q_producer(bias=qb, positive=[False, True], train_bias=train_bias)
+            ref_qt = q_producer(bias=qb, positive=[False, True], train_bias=train_bias)
         ref_init = policy_producer() if global_opt else None
         ref_tp = policy_producer()
         ref_init_tp = policy_producer() if global_opt else None
-        self._build(ref_pol, ref_q, ref_qt, ref_tp, policy_lr, qf_lr)
+        if self.unshared:
+            self._build(ref_pol, ref_q, ref_qt, ref_tp, policy_lr, [qf_lr, std_lr],
+                        positives=[False, True], frozen=[False, not train_bias])
+        else:
+            self._build(ref_pol, ref_q, ref_qt, ref_tp, policy_lr, qf_lr)
         self._make_init_policies(ref_init, ref_init_tp)
         self._make_target_policy_network(policy_producer)
         self.q, self.q_target = self.qfs[0], self.tfs[0]
         self.q_optimizer = self.qf_optimizers[0]
+        if self.unshared:
+            self.std, self.std_target = self.qfs[1], self.tfs[1]
+            self.std_optimizer = self.qf_optimizers[1]
 
     def _make_cfg(self, batch):
         c = super()._make_cfg(batch)
@@ -119,7 +138,10 @@ class GaussianTrainer(_TargetPolicyTrainer):
     # ------------------------------------------------------------ misc API
     def _qs(self, obs, action):
         with torch.no_grad():
-            out = self.q(self._tensor(obs), self._tensor(action))
+            obs, action = self._tensor(obs), self._tensor(action)
+            out = self.q(obs, action)
+            if self.unshared:   # gaussian_trainer.py:170-171: the std critic's own (exp'd) output
+                return out, self.std(obs, action)
         return out[:, 0].unsqueeze(-1), out[:, 1].unsqueeze(-1)
 
     def predict(self, obs, action, std=True):

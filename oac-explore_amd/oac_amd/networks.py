@@ -108,24 +108,31 @@ class ArenaFlattenMlp(nn.Module):
     """FlattenMlp (networks.py:154-161): relu hidden layers, identity output,
     inputs concatenated along dim 1."""
 
-    def __init__(self, arena, base, layout, obs_dim, act_dim, hidden, out_dim, positive=False):
+    def __init__(self, arena, base, layout, obs_dim, act_dim, hidden, out_dim, positive=False,
+                 stacked_index=None):
         super().__init__()
         L = layout
         self.positive = positive   # exp of the output (all, or per column), networks.py:69-75
         din = obs_dim + act_dim
         self.input_size, self.output_size = din, out_dim
-        self.fc0 = _ArenaLinear(_view(arena, base + L.q_fc0_w, hidden, din),
-                                _view(arena, base + L.q_fc0_b, hidden))
+        w0, b0, wl, bl = L.q_fc0_w, L.q_fc0_b, L.q_last_w, L.q_last_b
+        if stacked_index is not None:
+            # share_layers=False (oac_sac_config.unshared): critic k of the stacked
+            # one-hidden-layer critic block -- slice k of each stacked tensor
+            assert out_dim == 1 and L.q_fc1_w < 0
+            k = int(stacked_index)
+            w0, b0, wl, bl = w0 + k * hidden * din, b0 + k * hidden, wl + k * hidden, bl + k
+        self.fc0 = _ArenaLinear(_view(arena, base + w0, hidden, din), _view(arena, base + b0, hidden))
         self.fcs = [self.fc0]
         if L.q_fc1_w >= 0:   # (-1: a one-hidden-layer critic, no fc1 in the arena)
             self.fc1 = _ArenaLinear(_view(arena, base + L.q_fc1_w, hidden, hidden),
                                     _view(arena, base + L.q_fc1_b, hidden))
             self.fcs.append(self.fc1)
-        self.last_fc = _ArenaLinear(_view(arena, base + L.q_last_w, out_dim, hidden),
-                                    _view(arena, base + L.q_last_b, out_dim))
+        self.last_fc = _ArenaLinear(_view(arena, base + wl, out_dim, hidden),
+                                    _view(arena, base + bl, out_dim))
         self.arena, self.base = arena, base
         self.hidden, self.obs_dim, self.act_dim = hidden, obs_dim, act_dim
-        self._offs = _offsets(L.q_fc0_w, L.q_fc0_b, L.q_fc1_w, L.q_fc1_b, L.q_last_w, L.q_last_b)
+        self._offs = _offsets(w0, b0, L.q_fc1_w, L.q_fc1_b, wl, bl)
 
     def forward(self, *inputs, **kwargs):
         if len(inputs) == 2:

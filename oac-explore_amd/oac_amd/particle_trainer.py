@@ -37,19 +37,24 @@ class ParticleTrainer(_TargetPolicyTrainer):
                  std_soft_update_prob=0., train_bias=True, use_target_policy=False,
                  rescale_targets_around_mean=False,
                  device=None, seed=0, use_graph=False, gemm_cfg=-1):
-        unsupported = dict(share_layers=not share_layers, deterministic=not deterministic,
-                           ensemble=ensemble)
+        unsupported = dict(deterministic=not deterministic, ensemble=ensemble)
         bad = [k for k, v in unsupported.items() if v]
         if bad:
             raise NotImplementedError(
-                "oac_amd.ParticleTrainer implements the p-oac recipe configuration "
-                "(share_layers=True, deterministic policy, counts / std_soft_update / "
+                "oac_amd.ParticleTrainer implements the p-oac recipe configurations "
+                "(share_layers=True, or one critic per particle at one hidden layer; "
+                "deterministic policy, counts / std_soft_update / "
                 "mean_update / rescale_targets_around_mean / train_bias / "
                 f"use_target_policy, global_opt, no ensemble); unsupported: {bad}")
         assert not counts or not std_soft_update   # particle_trainer.py:92
         self._common_init(device, soft_target_tau, target_update_period, deterministic,
                           discount, reward_scale, policy_lr, qf_lr, use_graph, seed, gemm_cfg)
         self.train_bias = train_bias
+        self.unshared = not share_layers
+        if self.unshared and not 2 <= n_estimators <= 16:
+            raise NotImplementedError(
+                f"oac_amd.ParticleTrainer with share_layers=False takes 2 to 16 particles, got "
+                f"n_estimators={n_estimators}; unsupported: ['n_estimators']")
         # quantile bookkeeping, particle_trainer.py:61-69 (delta_index uses p - 1
         # when the quantile grid steps over delta)
         quantiles = [i * 1. / (n_estimators - 1) for i in range(n_estimators)]
@@ -62,7 +67,7 @@ class ParticleTrainer(_TargetPolicyTrainer):
                 break
         self.share_layers = share_layers
         self.num_particles = n_estimators
-        self.n_estimators = 1
+        self.n_estimators = n_estimators if self.unshared else 1   # particle_trainer.py:72-77
         self._q_out = n_estimators
         self.q_min, self.q_max, self.delta = q_min, q_max, delta
         self.r_mellow_max, self.b, self.mellow_max = r_mellow_max, b_mellow_max, mellow_max
@@ -77,16 +82,31 @@ class ParticleTrainer(_TargetPolicyTrainer):
         # and four critics (unused), the shared-layer critic and its target
         # (the target then copied from the critic, soft_update tau=1), then
         # target_policy (particle_trainer.py:47-59, 96-106, 141)
+        if self.unshared:
+            self._reject_unshared_options()
         ref_pol = policy_producer()
         for _ in range(4):
             q_producer()
         init_values = np.linspace(q_min, q_max, n_estimators)
-        ref_q = q_producer(bias=init_values, train_bias=train_bias)
-        q_producer(bias=init_values, train_bias=train_bias)
+        if self.unshared:
+            # particle_trainer.py:105-114: per particle a critic and its target
+            # (the target then copied from the critic), biased at its initial value
+            ref_q = []
+            for i in range(n_estimators):
+                ref_q.append(q_producer(bias=init_values[i], train_bias=train_bias))
+                q_producer(bias=init_values[i], train_bias=train_bias)
+        else:
+            ref_q = q_producer(bias=init_values, train_bias=train_bias)
+            q_producer(bias=init_values, train_bias=train_bias)
         ref_init = policy_producer() if global_opt else None
         ref_tp = policy_producer()
         ref_init_tp = policy_producer() if global_opt else None
-        self._build(ref_pol, ref_q, ref_q, ref_tp, policy_lr, qf_lr)
+        if self.unshared:
+            K = n_estimators
+            self._build(ref_pol, ref_q, ref_q, ref_tp, policy_lr, [qf_lr] * K,
+                        positives=[False] * K, frozen=[not train_bias] * K)
+        else:
+            self._build(ref_pol, ref_q, ref_q, ref_tp, policy_lr, qf_lr)
         self._make_init_policies(ref_init, ref_init_tp)
         self._make_target_policy_network(policy_producer)
 
@@ -115,7 +135,9 @@ class ParticleTrainer(_TargetPolicyTrainer):
         st["QF Unordered"] = np.float64(np.sum(np.argsort(qs, axis=1, kind="stable") != order))
         st["QF target Undordered"] = np.float64(
             np.sum(np.argsort(tq, axis=1, kind="stable") != order))
-        st["Q Loss"] = np.float32(np.sum(losses, dtype=np.float32) / np.float32(K))
+        # (:267 divides the summed loss by the particle count with share_layers only)
+        st["Q Loss"] = np.float32(np.sum(losses, dtype=np.float32)) if self.unshared else \
+            np.float32(np.sum(losses, dtype=np.float32) / np.float32(K))
         for i in range(K):
             st[f"QF{i} Loss"] = losses[i]
             self._stats(st, f"Q{i}Predictions", sorted_qs[i])
@@ -129,7 +151,11 @@ class ParticleTrainer(_TargetPolicyTrainer):
     # ------------------------------------------------------------ misc API
     def _sorted(self, obs, action):
         with torch.no_grad():
-            qs = self.qfs[0](self._tensor(obs), self._tensor(action)).t().unsqueeze(-1)
+            obs, action = self._tensor(obs), self._tensor(action)
+            if self.unshared:   # particle_trainer.py:163-166: one call per critic, stacked
+                qs = torch.stack([q(obs, action) for q in self.qfs], dim=0)
+            else:
+                qs = self.qfs[0](obs, action).t().unsqueeze(-1)
         return qs, torch.sort(qs, dim=0)[0]                     # [K, B, 1]
 
     def predict(self, obs, action, all_particles=False):

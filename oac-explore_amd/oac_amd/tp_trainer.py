@@ -6,6 +6,11 @@ trained ``target_policy`` -- g-oac ``GaussianTrainer``
 (policy, one shared-layer critic and its target, target_policy), the same
 optimizer set and the same snapshot keys; their steps run in liboac_amd
 (csrc/det_plan.hip) over the arena [policy | target_policy | critic].
+
+With ``share_layers=False`` (the reference's default; one hidden layer) the
+critic block holds the K separate one-output critics stacked -- q and std
+(g-oac) or one per particle (p-oac) -- and ``qfs`` / ``tfs`` /
+``qf_optimizers`` are K modules / optimizer views over their slices.
 """
 import ctypes
 import random
@@ -51,27 +56,65 @@ class _TargetPolicyTrainer(_ArenaTrainer):
         self.policy_lr, self.qf_lr = policy_lr, qf_lr
         self.use_graph, self.seed, self._gemm_cfg = use_graph, int(seed), gemm_cfg
 
-    def _build(self, ref_pol, ref_q, ref_qt, ref_tp, policy_lr, qf_lr):
+    unshared = False        # share_layers=False: separate one-output critics (oac_sac_config.unshared)
+    std_lr = 0.0
+
+    def _reject_unshared_options(self):
+        """share_layers=False runs as direct launches on one process, without
+        the policy sweep: the options it does not take, by name."""
+        bad = [k for k, v in dict(global_opt=self.global_opt, use_graph=self.use_graph).items() if v]
+        if bad:
+            raise NotImplementedError(
+                f"oac_amd.{type(self).__name__} with share_layers=False (separate critics, each "
+                f"with its own optimizer) does not implement {' / '.join(bad)}; unsupported: {bad}")
+
+    def _build(self, ref_pol, ref_q, ref_qt, ref_tp, policy_lr, qf_lr, positives=None, frozen=None):
         """Arena modules initialised from the producers' state_dicts, and the
-        reference's optimizer views (policy, target_policy, shared critic)."""
+        reference's optimizer views (policy, target_policy, shared critic).
+        share_layers=False (``self.unshared``): ``ref_q`` / ``ref_qt`` /
+        ``qf_lr`` / ``positives`` / ``frozen`` are lists over the K one-output
+        critics, stored stacked in one critic block (include/oac_amd.h), each
+        exposed through modules and an optimizer view of its own slices."""
         pol_sd = {k: v.detach() for k, v in ref_pol.state_dict().items()}
-        Do, Da, H, K, self.n_hidden = _dims_from_state(pol_sd, ref_q.state_dict(), depths=(1, 2))
+        q0 = ref_q[0] if self.unshared else ref_q
+        Do, Da, H, K, self.n_hidden = _dims_from_state(pol_sd, q0.state_dict(), depths=(1, 2))
+        if self.unshared and self.n_hidden != 1:
+            raise NotImplementedError(
+                f"oac_amd.{type(self).__name__}: share_layers=False is implemented for one hidden "
+                f"layer (--num_layers 1, the recipes that run without --share_layers); got "
+                f"{self.n_hidden} hidden layers; unsupported: ['share_layers', 'num_layers']")
         if self.n_hidden == 1 and H % 4:
             raise ValueError(f"one hidden layer: the width must be a multiple of 4, got {H}")
-        if K != self._q_out:
+        if self.unshared and K != 1:
+            raise ValueError(f"share_layers=False: q_producer must build critics with one output "
+                             f"(main.py:138-143), got {K}")
+        if not self.unshared and K != self._q_out:
             raise ValueError(f"share_layers: q_producer must build a critic with {self._q_out} "
                              f"outputs, got {K}")
         lay = self._alloc(Do, Da, H, self.device)
         self.policy = ArenaTanhGaussianPolicy(self.params, 0, lay, Do, Da, H)
         self.target_policy = ArenaTanhGaussianPolicy(self.params, lay.tpol_base, lay, Do, Da, H)
-        qf = ArenaFlattenMlp(self.params, lay.q1_base, lay, Do, Da, H, K, positive=self._positive)
-        tf = ArenaFlattenMlp(self.targets, 0, lay, Do, Da, H, K, positive=self._positive)
         self.policy.load_state_dict(pol_sd)
         self.target_policy.load_state_dict({k: v.detach() for k, v in ref_tp.state_dict().items()})
-        qf.load_state_dict({k: v.detach() for k, v in ref_q.state_dict().items()})
-        tf.load_state_dict({k: v.detach() for k, v in ref_qt.state_dict().items()})
         self.policy.oac_trainer = self
-        self.qfs, self.tfs = [qf], [tf]
+        if self.unshared:
+            assert lay.n_critics == self._q_out == len(ref_q) == len(ref_qt)
+            self.qfs, self.tfs = [], []
+            for k in range(self._q_out):
+                qf = ArenaFlattenMlp(self.params, lay.q1_base, lay, Do, Da, H, 1,
+                                     positive=positives[k], stacked_index=k)
+                tf = ArenaFlattenMlp(self.targets, 0, lay, Do, Da, H, 1,
+                                     positive=positives[k], stacked_index=k)
+                qf.load_state_dict({n: v.detach() for n, v in ref_q[k].state_dict().items()})
+                tf.load_state_dict({n: v.detach() for n, v in ref_qt[k].state_dict().items()})
+                self.qfs.append(qf)
+                self.tfs.append(tf)
+        else:
+            qf = ArenaFlattenMlp(self.params, lay.q1_base, lay, Do, Da, H, K, positive=self._positive)
+            tf = ArenaFlattenMlp(self.targets, 0, lay, Do, Da, H, K, positive=self._positive)
+            qf.load_state_dict({k: v.detach() for k, v in ref_q.state_dict().items()})
+            tf.load_state_dict({k: v.detach() for k, v in ref_qt.state_dict().items()})
+            self.qfs, self.tfs = [qf], [tf]
         tw = lambda other, mod: _twin_views(self.params, other, list(mod.parameters()))
         names = [n for n, _ in self.policy.named_parameters()]
         # deterministic policies: the log-std heads never get a gradient
@@ -87,11 +130,14 @@ class _TargetPolicyTrainer(_ArenaTrainer):
         self.policy_optimizer = popt(
             self.policy, (lambda: self._policy_opt_steps) if self.global_opt else None)
         self.target_policy_optimizer = popt(self.target_policy)
-        q_no_grad = [] if self.train_bias else \
-            [i for i, (n, _) in enumerate(qf.named_parameters()) if n == "last_fc.bias"]
-        self.qf_optimizers = [AdamStateView(self, list(qf.parameters()), tw(self.adam_m, qf),
-                                            tw(self.adam_v, qf), qf_lr, (0.9, 0.999), 1e-8,
-                                            no_grad=q_no_grad)]
+        self.qf_optimizers = []
+        for k, qf in enumerate(self.qfs):
+            frozen_k = frozen[k] if self.unshared else not self.train_bias
+            q_no_grad = [i for i, (n, _) in enumerate(qf.named_parameters())
+                         if n == "last_fc.bias"] if frozen_k else []
+            self.qf_optimizers.append(AdamStateView(
+                self, list(qf.parameters()), tw(self.adam_m, qf), tw(self.adam_v, qf),
+                qf_lr[k] if self.unshared else qf_lr, (0.9, 0.999), 1e-8, no_grad=q_no_grad))
         # SACTrainer's alpha (snapshot keys only)
         self.alpha_optimizer = AdamStateView(self, [self.log_alpha], [self.alpha_state[1:2]],
                                              [self.alpha_state[2:3]], policy_lr, (0.9, 0.999),
@@ -251,6 +297,8 @@ class _TargetPolicyTrainer(_ArenaTrainer):
         c.mean_update = int(bool(self.mean_update))
         c.freeze_q_bias = int(not self.train_bias)
         c.global_opt = int(bool(self.global_opt))
+        c.unshared = int(bool(self.unshared))
+        c.std_lr = float(self.std_lr or 0.0)
         return c
 
     @staticmethod
