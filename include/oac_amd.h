@@ -206,6 +206,9 @@ enum oac_ws_buffer {
                                     particle_trainer.py:236-241) or the std target
                                     (gaussian_trainer.py:238-242) */
 
+/* act_dim: the layout (and the exploration and evaluation entry points that
+ * read parameters through it) takes 1..63; oac_sac_create -- the gradient
+ * step -- takes 1..32 and says so otherwise. */
 int oac_sac_query_layout(const oac_sac_config* cfg, oac_sac_layout* out);
 int oac_sac_create(const oac_sac_config* cfg, const oac_sac_buffers* bufs, oac_sac** out);
 int oac_sac_destroy(oac_sac* h);
@@ -455,6 +458,17 @@ int oac_expl_set_host_io(oac_expl* h, const float* host_obs, float* host_out);
  * work already queued there) and returns once the results are in *out. */
 int oac_expl_host_staging(oac_expl* h, float** obs, float** out);
 int oac_expl_action_now(oac_expl* h, const float* eps, float beta_UB, float delta, void* stream);
+/* Which of the built kernel forms the handle's first launch takes (read-only,
+ * no GPU work): the first launch covers min(n_obs, 256) observations;
+ * single_call != 0 asks for oac_expl_action_now's launch instead of
+ * oac_expl_action's (they differ for n_obs == 1, obs_dim <= 512).  *kernel: 0
+ * the twin-critic kernel, 1 the split kernel; *group: workgroups per
+ * observation; *write_through: 1 static LDS with write-through hand-offs, 0
+ * dynamic LDS; *obs_in_args: 1 the observation travels in the kernel
+ * arguments and the outputs come back tagged.  Any output may be NULL.  The
+ * launchers act on the same decision. */
+int oac_expl_launch_form(oac_expl* h, int single_call, int* kernel, int* group, int* write_through,
+                         int* obs_in_args);
 /* --trainer_UB with particle_trainer_oac.ParticleTrainer (optimistic_exploration.py:38-39
  * -> trainer.predict(upper_bound=True), particle_trainer_oac.py:147-167): with a K-head
  * handle, index in [0, K) makes Q_UB = sort_k(Q_k)[index] (the trainer's delta_index;

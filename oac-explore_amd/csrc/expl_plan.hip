@@ -126,6 +126,9 @@ static int expl_sequence(ExplPlan& p, const float* eps, float beta, float delta,
   return 0;
 }
 
+// oac_expl_action_now's single-observation call (launch_expl_split_obs)
+static bool expl_single_obs(const ExplPlan& p) { return p.N == 1 && p.Do <= kExplObsArg; }
+
 static int expl_host_alloc(ExplPlan& p) {
   if (p.hc_obs) return 0;
   const unsigned fl = hipHostMallocCoherent | hipHostMallocMapped;
@@ -245,7 +248,12 @@ int oac_expl_create_batch(int n_obs, int obs_dim, int act_dim, int hidden, const
     set_error("oac_expl_create: null pointer");
     return 1;
   }
-  if (act_dim < 1 || act_dim > 63) { set_error("act_dim must be in [1, 63]"); return 1; }
+  if (obs_dim < 1) { set_error("exploration: obs_dim must be at least 1"); return 1; }
+  if (hidden < 1) { set_error("exploration: hidden must be at least 1"); return 1; }
+  if (act_dim < 1 || act_dim > 63) {
+    set_error("exploration: act_dim must be in [1, 63], got %d", act_dim);
+    return 1;
+  }
   if (n_obs < 1 || n_obs > 65536) { set_error("n_obs must be in [1, 65536]"); return 1; }
   if (expl_split_lds_bytes(obs_dim, act_dim, hidden) > 64 * 1024) {
     set_error("exploration: obs_dim + 4 * hidden too large for one workgroup's LDS");
@@ -376,7 +384,7 @@ int oac_expl_action_now(oac_expl* h, const float* eps, float beta_UB, float delt
   if (p.seq == 0) p.seq = 1;           // 0 is the word's initial value
   a.done = p.hc_done;
   a.done_seq = p.seq;
-  if (p.N == 1 && p.Do <= kExplObsArg) {   // one observation: it travels in the arguments,
+  if (expl_single_obs(p)) {                // one observation: it travels in the arguments,
     ExplObsArg o;                            // the outputs come back as tagged granules
     std::memcpy(o.v, p.hc_obs, sizeof(float) * p.Do);
     a.tags = p.hc_tag;
@@ -385,6 +393,22 @@ int oac_expl_action_now(oac_expl* h, const float* eps, float beta_UB, float delt
   }
   if (expl_launch(p, a, s)) return 1;
   return expl_wait(p, a.done_seq, s);
+}
+
+int oac_expl_launch_form(oac_expl* h, int single_call, int* kernel, int* group, int* write_through,
+                         int* obs_in_args) {
+  if (!h) { set_error("null handle"); return 1; }
+  ExplPlan& p = h->p;
+  // (the form depends on the dimensions and the critic count alone)
+  const ExplFusedArgs a = expl_args(p, nullptr, 0.f, 0.f);
+  const ExplForm f =
+      expl_launch_form(a, std::min(kExplRows, p.N), single_call != 0 && expl_single_obs(p));
+  if (!f.fits) { set_error("exploration: no kernel form takes these dimensions"); return 1; }
+  if (kernel) *kernel = f.split ? 1 : 0;
+  if (group) *group = f.group;
+  if (write_through) *write_through = f.wt ? 1 : 0;
+  if (obs_in_args) *obs_in_args = f.obs_arg ? 1 : 0;
+  return 0;
 }
 
 const float* oac_expl_outputs(oac_expl* h) { return h ? h->p.ws + h->p.o_out : nullptr; }

@@ -241,12 +241,12 @@ __host__ __device__ inline long expl_split_scratch(int H) {
   const long twin = 2L * kTwinParts * H + 2L * H + 128;
   return split > twin ? split : twin;
 }
-// LDS floats: x | v1 [2H] | v2 [2H] | head [64] | misc [128] | partials [threads] |
+// LDS floats: x | v1 [2H] | v2 [2H] | head [128] | misc [128] | partials [threads] |
 // a part's dh1 columns | their da products
 __host__ __device__ inline long expl_split_lds(int Do, int Da, int H, int threads) {
   // the dh1 columns of one workgroup (G = 1: all 2H) and a part's da products
   const long w = (2L * H + kExplParts - 1) / kExplParts;
-  return ((Do + Da + 3) & ~3L) + 4L * H + 64 + 128 + threads + (2L * H + 32) + w * 64;
+  return ((Do + Da + 3) & ~3L) + 4L * H + 128 + 128 + threads + (2L * H + 32) + w * 64;
 }
 constexpr int kWtLdsFloats = 21 * 1024;   // 84 KB: one workgroup per CU
 // OBS: the (single) observation is the argument `oa` (launch_expl_split_obs)
@@ -280,8 +280,8 @@ __global__ void __launch_bounds__(1024) oac_expl_split_kernel(ExplFusedArgs a, i
   float* x = sm;                           // [Do + Da] ob | a
   float* v1 = x + ((Dq + 3) & ~3);         // [2H] scratch vectors
   float* v2 = v1 + 2 * H;                  // [2H]
-  float* head = v2 + 2 * H;                // [64] mean | raw log std
-  float* misc = head + 64;                 // [128] q, seeds, norm, K heads, reductions
+  float* head = v2 + 2 * H;                // [128] mean | raw log std (2 Da <= 126)
+  float* misc = head + 128;                // [128] q, seeds, norm, K heads, reductions
   float* qk = misc + 16;                   // [16] K head values
   float* wk = qk + 16;                     // [16] K head seeds
   float* red = misc + 64;                  // [64]
@@ -480,8 +480,11 @@ __global__ void __launch_bounds__(1024) oac_expl_split_kernel(ExplFusedArgs a, i
       // threads/32 parts (thread: column c, part pp; coalesced along the columns),
       // the parts added in order; then the part's partial of da = dh1 . W0[:, Do:]
       // (its columns in order), published for S5
-    float* dcol = prt + nt;   // [R / G + 32] dh1 of this workgroup's columns
-    float* prod = dcol + (2 * H + G - 1) / G + 32;   // [part width][Da]
+    // (dcol sized by the columns this workgroup owns: with G no divisor of
+    // kExplParts a workgroup owns ceil(kExplParts / G) parts, more than R / G
+    // + 32 columns from 2H = 1196 at G = 28; the columns then ran into prod)
+    float* dcol = prt + nt;   // [hi4 - lo4] dh1 of this workgroup's columns
+    float* prod = dcol + (hi4 - lo4);   // [part width][Da]
     for (int cb = lo4; cb < hi4; cb += 32) {
       const int e = cb + c4;
       float s = 0.f;
@@ -1177,54 +1180,71 @@ int expl_split_group(int n_rows) {
 // the twin-critic kernel off (tools/micro/expl_micro's A/B against the split kernel)
 bool g_expl_twin_off = false;
 
+// The form a launch of n_rows observations takes -- the one decision both
+// launchers below act on.  obs_arg: a single-observation call whose
+// observation may travel in the kernel arguments (the write-through forms
+// only; otherwise the call reads its host row like any other).
+ExplForm expl_launch_form(const ExplFusedArgs& a, int n_rows, bool obs_arg) {
+  ExplForm f{};
+  const int nt = expl_split_threads();
+  f.group = expl_split_group(n_rows);
+  // write-through hand-offs need every workgroup of the launch on a CU of its own
+  const bool own_cu = f.group > 1 && (long)n_rows * f.group <= expl_device_cus();
+  if (!g_expl_twin_off && expl_twin_ok(a, nt, own_cu)) {
+    f.split = false;
+    f.wt = own_cu;
+    f.lds_bytes = own_cu ? 0 : expl_twin_lds(a.Do, a.Da, a.H, nt) * sizeof(float);
+    f.fits = true;
+  } else {
+    const long lds = expl_split_lds(a.Do, a.Da, a.H, nt);
+    f.split = true;
+    f.wt = own_cu && lds <= kWtLdsFloats;
+    f.lds_bytes = f.wt ? 0 : lds * sizeof(float);
+    f.fits = f.lds_bytes <= 64 * 1024;
+  }
+  f.obs_arg = obs_arg && f.wt;
+  return f;
+}
+
+static hipError_t launch_expl_form(const ExplForm& f, const ExplFusedArgs& a, int row0, int n_rows,
+                                   float* scratch, const ExplObsArg& obs, hipStream_t s) {
+  if (!f.fits) return hipErrorInvalidValue;
+  const int nt = expl_split_threads(), G = f.group;
+  const dim3 grid(n_rows * G), block(nt);
+  if (!f.split) {
+    if (f.obs_arg)
+      OAC_LAUNCH((oac_expl_twin_kernel<true, true>), grid, block, 0, s, a, row0, G, scratch, obs);
+    else if (f.wt)
+      OAC_LAUNCH((oac_expl_twin_kernel<true, false>), grid, block, 0, s, a, row0, G, scratch, obs);
+    else
+      OAC_LAUNCH((oac_expl_twin_kernel<false, false>), grid, block, f.lds_bytes, s, a, row0, G,
+                 scratch, obs);
+  } else {
+    if (f.obs_arg)
+      OAC_LAUNCH((oac_expl_split_kernel<true, true>), grid, block, 0, s, a, row0, G, scratch, obs);
+    else if (f.wt)
+      OAC_LAUNCH((oac_expl_split_kernel<true, false>), grid, block, 0, s, a, row0, G, scratch, obs);
+    else
+      OAC_LAUNCH((oac_expl_split_kernel<false, false>), grid, block, f.lds_bytes, s, a, row0, G,
+                 scratch, obs);
+  }
+  return hipGetLastError();
+}
+
 // rows [row0, row0 + n_rows) of the call, one group of G workgroups each
 hipError_t launch_expl_split(const ExplFusedArgs& a, int row0, int n_rows, float* scratch,
                              hipStream_t s) {
   if (n_rows < 1 || n_rows > kExplRows || a.Da < 1 || a.Da > 63 || a.H < 1 || a.K > 16)
     return hipErrorInvalidValue;
-  const int nt = expl_split_threads();
-  const int G = expl_split_group(n_rows);
   static const ExplObsArg none{};   // (unread)
-  // write-through hand-offs need every workgroup of the launch on a CU of its own
-  const bool own_cu = G > 1 && (long)n_rows * G <= expl_device_cus();
-  if (!g_expl_twin_off && expl_twin_ok(a, nt, own_cu)) {
-    if (own_cu) {
-      OAC_LAUNCH((oac_expl_twin_kernel<true, false>), dim3(n_rows * G), dim3(nt), 0, s, a, row0, G,
-                 scratch, none);
-    } else {
-      OAC_LAUNCH((oac_expl_twin_kernel<false, false>), dim3(n_rows * G), dim3(nt),
-                 expl_twin_lds(a.Do, a.Da, a.H, nt) * sizeof(float), s, a, row0, G, scratch, none);
-    }
-    return hipGetLastError();
-  }
-  const long lds = expl_split_lds(a.Do, a.Da, a.H, nt);
-  const bool wt = own_cu && lds <= kWtLdsFloats;
-  if (wt) {
-    OAC_LAUNCH((oac_expl_split_kernel<true, false>), dim3(n_rows * G), dim3(nt), 0, s, a, row0, G,
-               scratch, none);
-  } else {
-    if (lds * sizeof(float) > 64 * 1024) return hipErrorInvalidValue;
-    OAC_LAUNCH((oac_expl_split_kernel<false, false>), dim3(n_rows * G), dim3(nt), lds * sizeof(float),
-               s, a, row0, G, scratch, none);
-  }
-  return hipGetLastError();
+  return launch_expl_form(expl_launch_form(a, n_rows, false), a, row0, n_rows, scratch, none, s);
 }
 
 hipError_t launch_expl_split_obs(const ExplFusedArgs& a, const ExplObsArg& obs, float* scratch,
                                  hipStream_t s) {
   if (a.n != 1 || a.Do > kExplObsArg || a.Da < 1 || a.Da > 63 || a.H < 1 || a.K > 16)
     return hipErrorInvalidValue;
-  const int nt = expl_split_threads();
-  const int G = expl_split_group(1);
-  const bool own_cu = G > 1 && G <= expl_device_cus();
-  if (own_cu && !g_expl_twin_off && expl_twin_ok(a, nt, true)) {
-    OAC_LAUNCH((oac_expl_twin_kernel<true, true>), dim3(G), dim3(nt), 0, s, a, 0, G, scratch, obs);
-    return hipGetLastError();
-  }
-  const long lds = expl_split_lds(a.Do, a.Da, a.H, nt);
-  if (!(own_cu && lds <= kWtLdsFloats)) return launch_expl_split(a, 0, 1, scratch, s);
-  OAC_LAUNCH((oac_expl_split_kernel<true, true>), dim3(G), dim3(nt), 0, s, a, 0, G, scratch, obs);
-  return hipGetLastError();
+  return launch_expl_form(expl_launch_form(a, 1, true), a, 0, 1, scratch, obs, s);
 }
 
 }  // namespace oac

@@ -162,6 +162,17 @@ constexpr int kExplObsArg = 512;
 struct ExplObsArg { float v[kExplObsArg]; };
 hipError_t launch_expl_split_obs(const ExplFusedArgs& a, const ExplObsArg& obs, float* scratch,
                                  hipStream_t s);
+// which of the built forms a launch of n_rows observations takes (the two
+// launchers above launch what this returns; oac_expl_launch_form reports it)
+struct ExplForm {
+  bool split;        // oac_expl_split_kernel (else oac_expl_twin_kernel)
+  int group;         // workgroups per observation
+  bool wt;           // static LDS, write-through hand-offs (else dynamic LDS)
+  bool obs_arg;      // the observation in the kernel arguments, tagged outputs
+  size_t lds_bytes;  // dynamic LDS (0 with wt)
+  bool fits;         // false: no form takes these dimensions
+};
+ExplForm expl_launch_form(const ExplFusedArgs& a, int n_rows, bool obs_arg);
 
 // row-wise network evaluation off the gradient step (mlp_eval.hip)
 struct MlpEvalArgs {

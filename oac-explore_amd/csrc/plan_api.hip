@@ -274,7 +274,9 @@ static int validate(const oac_sac_config* c) {
       return 1;
     }
   }
-  if (c->obs_dim < 1 || c->act_dim < 1 || c->act_dim > 32 || c->hidden < 1 || c->batch < 1) {
+  // (the layout and the exploration / evaluation kernels that read it take
+  // act_dim <= 63; the gradient step takes 32: oac_sac_create)
+  if (c->obs_dim < 1 || c->act_dim < 1 || c->act_dim > 63 || c->hidden < 1 || c->batch < 1) {
     set_error("bad dims obs=%d act=%d hidden=%d batch=%d", c->obs_dim, c->act_dim, c->hidden, c->batch);
     return 1;
   }
@@ -356,6 +358,11 @@ int oac_sac_query_layout(const oac_sac_config* cfg, oac_sac_layout* out) {
 
 int oac_sac_create(const oac_sac_config* cfg, const oac_sac_buffers* bufs, oac_sac** out) {
   if (validate(cfg)) return 1;
+  if (cfg->act_dim > 32) {   // rows.hip: one half-wave lane per action dim
+    set_error("the gradient step takes act_dim <= 32, got %d (the parameter layout, exploration "
+              "and evaluation take up to 63)", cfg->act_dim);
+    return 1;
+  }
   if (!bufs || !out) { set_error("null buffers/out"); return 1; }
   oac_sac* h = new oac_sac();
   SacPlan& p = h->plan;

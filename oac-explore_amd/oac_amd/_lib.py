@@ -249,6 +249,11 @@ _SIGS = {
                                              ctypes.POINTER(ctypes.c_void_p)]),
     "oac_expl_action_now": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_float,
                                            ctypes.c_float, ctypes.c_void_p]),
+    "oac_expl_launch_form": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int,
+                                            ctypes.POINTER(ctypes.c_int),
+                                            ctypes.POINTER(ctypes.c_int),
+                                            ctypes.POINTER(ctypes.c_int),
+                                            ctypes.POINTER(ctypes.c_int)]),
 }
 
 # every symbol include/oac_amd.h declares (checked by tests/test_abi.py)

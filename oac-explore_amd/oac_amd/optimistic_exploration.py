@@ -65,7 +65,8 @@ def get_optimistic_exploration_action(ob_np, policy=None, qfs=None, trainer=None
     beta_UB*|Q1-Q2|/2 as the qfs branch (trainer/trainer.py:105-123); for the
     P-OAC ParticleTrainer the head sorted at its delta_index
     (particle_trainer_oac.py:147-167, oac_expl_set_ub_index).  ``eps`` (float32[Da]) replaces the device Philox draw for parity
-    runs; ``return_info`` adds mu_E / std / grad to the info dict."""
+    runs; ``return_info`` adds mu_E / std to the info dict (dQ_UB/dmu_T stays on
+    the device: ``oac_expl_action``'s ``grad_out`` returns it)."""
     if deterministic:
         raise NotImplementedError("the deterministic OAC variant is unreachable from rollout() "
                                   "(SURVEY 8a quirk Q7) and not implemented")
