@@ -25,6 +25,8 @@
  *   OAC_KIND_DDPG         DDPGTrainer.train_from_torch (--alg ddpg; one critic, the
  *                         deterministic policy, optional frozen target_policy_network;
  *                         trainer/ddpg_trainer.py:92-184)
+ *   OAC_KIND_SAC_SHALLOW  SACTrainer.train_from_torch with one-hidden-layer networks
+ *                         (main.py's --alg oac --num_layers 1 default; oac.sh, sac.sh)
  *   oac_policy_eval_fixed_std   TanhGaussianPolicy.forward with a fixed std
  *                         (trainer/policies.py:244-249, 280-282; main.py:144-149)
  *   oac_expl_action       get_optimistic_exploration_action (stochastic branch)
@@ -53,17 +55,26 @@ enum oac_kind {
   OAC_KIND_GAUSS = 2,        /* gaussian_trainer.GaussianTrainer (g-oac)       */
   OAC_KIND_PARTICLE_UB = 3,  /* particle_trainer.ParticleTrainer (p-oac recipes: deterministic
                                 policy, upper-bound quantile loss, target_policy) */
-  OAC_KIND_DDPG = 4          /* ddpg_trainer.DDPGTrainer (--alg ddpg): one critic with q_out=1,
+  OAC_KIND_DDPG = 4,         /* ddpg_trainer.DDPGTrainer (--alg ddpg): one critic with q_out=1,
                                 deterministic policy, no target_policy block; single-process
                                 only (oac_sac_step_phase / _set_allreduce / _set_step_graph
                                 and OAC_STEP_USE_GRAPH are rejected for this kind) */
+  OAC_KIND_SAC_SHALLOW = 5   /* SACTrainer (OAC / SAC) with ONE hidden layer (--num_layers 1):
+                                twin critics with q_out=1, tanh-Gaussian policy; n_hidden must
+                                be 1, hidden a multiple of 4; the layout is OAC_KIND_SAC's
+                                without the fc1 tensors.  Single-process, small-batch kernel
+                                set only (a batch that selects the large-batch set is
+                                rejected by oac_sac_create), and, as OAC_KIND_DDPG,
+                                oac_sac_step_phase / _set_allreduce / _set_step_graph and
+                                OAC_STEP_USE_GRAPH are rejected */
 };
 
 typedef struct oac_sac_config {
   int kind;              /* OAC_KIND_SAC (twin critics, q_out=1); OAC_KIND_PARTICLE and
                             OAC_KIND_PARTICLE_UB (one critic, q_out = K particles);
                             OAC_KIND_GAUSS (one critic, q_out=2: mean | log std);
-                            OAC_KIND_DDPG (one critic, q_out=1) */
+                            OAC_KIND_DDPG (one critic, q_out=1);
+                            OAC_KIND_SAC_SHALLOW (twin critics, q_out=1, n_hidden=1) */
   int obs_dim, act_dim;
   int hidden;            /* width of every hidden layer (reference: [M]*N; N = n_hidden) */
   int q_out;             /* 1 for SAC/OAC; K heads for the shared-layer particle critic */
@@ -94,7 +105,8 @@ typedef struct oac_sac_config {
   int freeze_q_bias;
   /* hidden layers of the policy and of the critic: 0 (a zero-initialised
    * config) or 2 = the two-layer networks; 1 = one hidden layer, for
-   * OAC_KIND_GAUSS and OAC_KIND_PARTICLE_UB only (main.py's --num_layers 1
+   * OAC_KIND_GAUSS, OAC_KIND_PARTICLE_UB and OAC_KIND_SAC_SHALLOW (which takes
+   * nothing else) only (main.py's --num_layers 1
    * default, the riverswim recipes).  At 1 the layout has no fc1 tensors:
    * pol_fc1_* and q_fc1_* are -1; hidden must then be a multiple of 4 */
   int n_hidden;
@@ -429,6 +441,14 @@ int64_t oac_expl_workspace_floats_batch(int n_obs, int obs_dim, int act_dim, int
 int oac_expl_create_batch(int n_obs, int obs_dim, int act_dim, int hidden, const float* policy,
                           const float* q1, const float* q2, float* workspace, void* step_state,
                           uint64_t seed, oac_expl** out);
+/* twin critics and a policy of ONE hidden layer (the networks of OAC_KIND_SAC_SHALLOW:
+ * policy / q1 / q2 point at their blocks of that kind's layout): the same action by one
+ * workgroup per observation with no hand-off between workgroups.  hidden % 4 == 0, hidden
+ * <= 512, act_dim <= 63; workspace: oac_expl_workspace_floats_batch() floats.  Every other
+ * oac_expl_* call takes such a handle, except oac_expl_set_ub_index (no K-head form) */
+int oac_expl_create_shallow(int n_obs, int obs_dim, int act_dim, int hidden, const float* policy,
+                            const float* q1, const float* q2, float* workspace, void* step_state,
+                            uint64_t seed, oac_expl** out);
 /* one critic with K heads (share_layers, K in [2, 16]): Q_UB = mean_k Q_k + beta_UB std_k Q_k
  * (unbiased std; optimistic_exploration.py:48-58, the except branch taken when qfs has
  * one shared-layer critic); q points at its block in a K-head critic layout */
@@ -462,7 +482,8 @@ int oac_expl_action_now(oac_expl* h, const float* eps, float beta_UB, float delt
  * no GPU work): the first launch covers min(n_obs, 256) observations;
  * single_call != 0 asks for oac_expl_action_now's launch instead of
  * oac_expl_action's (they differ for n_obs == 1, obs_dim <= 512).  *kernel: 0
- * the twin-critic kernel, 1 the split kernel; *group: workgroups per
+ * the twin-critic kernel, 1 the split kernel, 2 the one-hidden-layer kernel
+ * (oac_expl_create_shallow; *group 1, *write_through 0); *group: workgroups per
  * observation; *write_through: 1 static LDS with write-through hand-offs, 0
  * dynamic LDS; *obs_in_args: 1 the observation travels in the kernel
  * arguments and the outputs come back tagged.  Any output may be NULL.  The

@@ -9,8 +9,9 @@
 //   action = tanh(mu_E + std * eps),  mu_E = mu_T + mu_C
 // The critics and policy are read in place from the trainer's parameter arena,
 // so the action always uses the current weights.  The computation is one
-// launch (expl_split.hip: a group of workgroups per observation).  Two ways to
-// call it:
+// launch (expl_split.hip: a group of workgroups per observation; networks of one
+// hidden layer, oac_expl_create_shallow: expl_shallow.hip, one workgroup per
+// observation).  Two ways to call it:
 //   oac_expl_action      a captured hipGraph (with the observation upload and
 //                        result download when pinned buffers are registered),
 //                        replayed on the caller's stream;
@@ -25,6 +26,7 @@
 #include <cstdlib>
 
 #include "../../include/oac_amd.h"
+#include "expl_shallow.h"
 #include "kernels.h"
 #include "oac_common.h"
 
@@ -35,6 +37,9 @@ static inline int64_t a64(int64_t x) { return (x + 63) & ~int64_t(63); }
 struct ExplPlan {
   int Do, Da, H, N = 1;
   int K = 1;   // critic heads: 1 with twin critics (q1, q2); K with one shared-layer critic (q2 null)
+  // one-hidden-layer networks (oac_expl_create_shallow): expl_shallow.hip's
+  // kernel, one workgroup per observation, in place of expl_split.hip's forms
+  bool shallow = false;
   int ub_index = -1;   // K heads: sorted-head upper bound (oac_expl_set_ub_index)
   const float* pol; const float* q1; const float* q2;
   float* ws;
@@ -107,6 +112,10 @@ static ExplFusedArgs expl_args(ExplPlan& p, const float* eps, float beta, float 
 }
 
 static int expl_launch(ExplPlan& p, const ExplFusedArgs& a, hipStream_t s) {
+  if (p.shallow) {   // every observation in one launch
+    OAC_HIP_CHECK(launch_expl_shallow(a, s));
+    return 0;
+  }
   for (int row0 = 0; row0 < p.N; row0 += kExplRows)
     OAC_HIP_CHECK(launch_expl_split(a, row0, std::min(kExplRows, p.N - row0), p.ws + p.o_split, s));
   return 0;
@@ -298,6 +307,55 @@ int oac_expl_create_shared(int n_obs, int obs_dim, int act_dim, int hidden, int 
   return 0;
 }
 
+int oac_expl_create_shallow(int n_obs, int obs_dim, int act_dim, int hidden, const float* policy,
+                            const float* q1, const float* q2, float* workspace, void* step_state,
+                            uint64_t seed, oac_expl** out) {
+  if (!policy || !q1 || !q2 || !workspace || !step_state || !out) {
+    set_error("oac_expl_create_shallow: null pointer");
+    return 1;
+  }
+  if (obs_dim < 1) { set_error("exploration (one hidden layer): obs_dim must be at least 1"); return 1; }
+  if (act_dim < 1 || act_dim > 63) {
+    set_error("exploration (one hidden layer): act_dim must be in [1, 63], got %d", act_dim);
+    return 1;
+  }
+  if (hidden < 4 || hidden > kExplShallowMaxH || (hidden & 3)) {
+    set_error("exploration (one hidden layer): hidden must be a multiple of 4 in [4, %d], got %d",
+              kExplShallowMaxH, hidden);
+    return 1;
+  }
+  if (n_obs < 1 || n_obs > 65536) {
+    set_error("exploration (one hidden layer): n_obs must be in [1, 65536], got %d", n_obs);
+    return 1;
+  }
+  // (the same obs_dim bound as the two-layer forms, and this kernel's own LDS)
+  if (expl_split_lds_bytes(obs_dim, act_dim, hidden) > 64 * 1024 ||
+      expl_shallow_lds_bytes(obs_dim, act_dim, hidden) > 64 * 1024) {
+    set_error("exploration (one hidden layer): obs_dim %d too large for one workgroup's LDS "
+              "(hidden %d)", obs_dim, hidden);
+    return 1;
+  }
+  oac_sac_config c;
+  std::memset(&c, 0, sizeof(c));
+  c.kind = OAC_KIND_SAC_SHALLOW; c.n_hidden = 1;
+  c.obs_dim = obs_dim; c.act_dim = act_dim; c.hidden = hidden; c.q_out = 1;
+  c.batch = 1; c.row_stride = ((2 * obs_dim + act_dim + 2 + 3) / 4) * 4;
+  c.off_obs = 0; c.off_act = obs_dim; c.off_rew = obs_dim + act_dim; c.off_term = c.off_rew + 1;
+  c.off_next_obs = c.off_term + 1; c.gemm_cfg = 0; c.world_size = 1;
+  oac_sac_layout L;
+  if (oac_sac_query_layout(&c, &L)) return 1;
+  oac_expl* h = new oac_expl();
+  ExplPlan& p = h->p;
+  p.shallow = true;
+  p.Do = obs_dim; p.Da = act_dim; p.H = hidden; p.N = n_obs;
+  p.pol = policy; p.q1 = q1; p.q2 = q2; p.ws = workspace;
+  p.state = reinterpret_cast<StepState*>(step_state); p.seed = seed;
+  p.L = L;
+  expl_layout(p);
+  *out = h;
+  return 0;
+}
+
 int oac_expl_create(int obs_dim, int act_dim, int hidden, const float* policy, const float* q1,
                     const float* q2, float* workspace, void* step_state, uint64_t seed,
                     oac_expl** out) {
@@ -388,7 +446,8 @@ int oac_expl_action_now(oac_expl* h, const float* eps, float beta_UB, float delt
     ExplObsArg o;                            // the outputs come back as tagged granules
     std::memcpy(o.v, p.hc_obs, sizeof(float) * p.Do);
     a.tags = p.hc_tag;
-    OAC_HIP_CHECK(launch_expl_split_obs(a, o, p.ws + p.o_split, s));
+    if (p.shallow) OAC_HIP_CHECK(launch_expl_shallow_obs(a, o, s));
+    else OAC_HIP_CHECK(launch_expl_split_obs(a, o, p.ws + p.o_split, s));
     return expl_wait_tags(p, a.done_seq, s);
   }
   if (expl_launch(p, a, s)) return 1;
@@ -399,6 +458,13 @@ int oac_expl_launch_form(oac_expl* h, int single_call, int* kernel, int* group, 
                          int* obs_in_args) {
   if (!h) { set_error("null handle"); return 1; }
   ExplPlan& p = h->p;
+  if (p.shallow) {   // one kernel, one workgroup per observation, dynamic LDS
+    if (kernel) *kernel = 2;
+    if (group) *group = 1;
+    if (write_through) *write_through = 0;
+    if (obs_in_args) *obs_in_args = (single_call != 0 && expl_single_obs(p)) ? 1 : 0;
+    return 0;
+  }
   // (the form depends on the dimensions and the critic count alone)
   const ExplFusedArgs a = expl_args(p, nullptr, 0.f, 0.f);
   const ExplForm f =
@@ -416,6 +482,11 @@ const float* oac_expl_outputs(oac_expl* h) { return h ? h->p.ws + h->p.o_out : n
 int oac_expl_set_ub_index(oac_expl* h, int index) {
   if (!h) { set_error("null handle"); return 1; }
   ExplPlan& p = h->p;
+  if (p.shallow) {
+    set_error("oac_expl_set_ub_index: a one-hidden-layer handle (oac_expl_create_shallow) has twin "
+              "critics only; there is no K-head form at one hidden layer");
+    return 1;
+  }
   if (index < -1 || index >= p.K || (index >= 0 && p.q2)) {
     set_error("ub index %d: needs a K-head handle and -1 <= index < K (K = %d)", index, p.K);
     return 1;

@@ -390,6 +390,40 @@ struct DdpgHeadBwdArgs {
 };
 hipError_t launch_ddpg_head_backward(const DdpgHeadBwdArgs& a, hipStream_t s);
 
+// SAC / OAC with one hidden layer (sac_shallow_plan.hip): the six width-1 last
+// layers of the step -- Q_i(obs, a), Q_i(obs, a~), QT_i(next_obs, a'), QV_*
+// order, all with pre-step weights -- evaluated here (row_heads, K = 1), then
+// critic_targets_kernel's row math on them (t: the alpha update, y, dq_i, the
+// -min Q seeds gq_i, sqe_i, qnew; t.n_part == 0 and t.q[k] == head[k].out), then
+// the critics' backward into their hidden layer,
+//   dh1q[i][r, n] = [h1q_i[r, n] > 0] dq_i[r] w_last_i[n]   (h1q_i = head[i].h,
+//   w_last_i = head[i].w; float4 columns: H % 4 == 0)
+struct SacShallowTargetArgs {
+  CriticTargetArgs t;
+  RowHead head[QV_COUNT];
+  float* dh1q[2];                       // [B, H]
+};
+hipError_t launch_sac_shallow_targets(const SacShallowTargetArgs& a, hipStream_t s);
+
+// ... and the policy loss mean(alpha logp - min Q) from the hidden layer of
+// Q_i(obs, a~) back to the policy heads in one launch, through the POST-step
+// critics with the PRE-step activations as masks (the reference's torch-1.4
+// order).  Per row r:
+//   dh1n_i[n] = [h1n_i[r, n] > 0] gq_i[r] wl_i[n]
+//   da[j]     = sum_i sum_n dh1n_i[n] wa_i[n, j]      (wa_i = W0_i[:, Do:], row n at wa_i + n ld_wa)
+//   dhead[r]  = tanh_gauss_backward(da, ...; G = alpha / B)   (policy_math.h: dmean | d raw log std)
+// replacing the -min Q dX, the dL/da product and the head-backward epilogue.
+struct SacShallowPolicyBwdArgs {
+  const float* h1n[2]; const float* gq[2];   // [B, H], [B]
+  const float* wl[2]; const float* wa[2]; long ld_wa;
+  const float* act; const float* stdv; const float* u; const float* eps;   // [B, Da]
+  const float* head;                    // [B, 2 Da] (raw log std for the clamp mask)
+  const AlphaState* alpha;              // null -> alpha = 0
+  float* dhead;                         // [B, 2 Da]
+  int B, H, Da;
+};
+hipError_t launch_sac_shallow_policy_backward(const SacShallowPolicyBwdArgs& a, hipStream_t s);
+
 // share_layers=False (det_plan.hip, unshared): the stacked critics' last-layer
 // gradient and the whole critic block's optimizer step in one launch.
 //   dw[n] = sum_r dq[r, n / Hs] h[r, n],  db[k] = sum_r dq[r, k]  (rows in a

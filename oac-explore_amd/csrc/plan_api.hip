@@ -3,8 +3,9 @@
 // trainer kind, handle create / destroy, the step entry points with their
 // graph capture, the host index ring, the data-parallel driver, timing and
 // workspace views.  What differs between the kinds -- workspace layout and
-// launch sequence -- lives in sac_plan.hip, particle_plan.hip, det_plan.hip
-// and ddpg_plan.hip, and is reached through one table (kind_ops).
+// launch sequence -- lives in sac_plan.hip, particle_plan.hip, det_plan.hip,
+// ddpg_plan.hip and sac_shallow_plan.hip, and is reached through one table
+// (kind_ops).
 #include <algorithm>
 #include <cstdarg>
 #include <cstdio>
@@ -72,7 +73,7 @@ static void compute_layout(const oac_sac_config& c, oac_sac_layout& L) {
   L.q_last_w = q; q = al4(q + Q * H);
   L.q_last_b = q; q = al4(q + Q);
   L.q_size = q;
-  L.n_critics = (c.kind == OAC_KIND_SAC) ? 2 : 1;
+  L.n_critics = twin_critics(c.kind) ? 2 : 1;
   // GAUSS: the target_policy block follows the policy, so both policies form
   // one Adam group (same lr, same step) in front of the critic
   L.tpol_base = has_target_policy(c.kind) ? L.pol_size : -1;
@@ -87,22 +88,30 @@ static int own_buffers(int which) { return which; }
 
 const KindOps& kind_ops(int kind) {
   static_assert(OAC_KIND_SAC == 0 && OAC_KIND_PARTICLE == 1 && OAC_KIND_GAUSS == 2 &&
-                OAC_KIND_PARTICLE_UB == 3 && OAC_KIND_DDPG == 4, "the table is indexed by kind");
+                OAC_KIND_PARTICLE_UB == 3 && OAC_KIND_DDPG == 4 && OAC_KIND_SAC_SHALLOW == 5,
+                "the table is indexed by kind");
   static const KindOps ops[] = {
       {sac_layout_workspace, sac_run_step, sac_step_phase, sac_ws_alias, sac_shadow_ws(), true},
       {particle_layout_workspace, particle_run_step, particle_step_phase, particle_ws_alias, -1, false},
       {det_layout_workspace, det_run_step, det_step_phase, own_buffers, -1, false},   // GAUSS
       {det_layout_workspace, det_run_step, det_step_phase, own_buffers, -1, false},   // PARTICLE_UB
       {ddpg_layout_workspace, ddpg_run_step, nullptr, ddpg_ws_alias, ddpg_shadow_ws(), false},
+      {sac_shallow_layout_workspace, sac_shallow_run_step, nullptr, sac_shallow_ws_alias, -1, false},
   };
+  static_assert(sizeof(ops) / sizeof(ops[0]) == kNumKinds, "one entry per kind");
   return ops[kind];
 }
 
-// A kind without a data-parallel step (DDPG) is single-process: its
-// data-parallel entry points fail by name.
+// the kinds' names in messages, indexed by kind (validated: < kNumKinds)
+static const char* const kKindNames[] = {"SAC", "PARTICLE", "GAUSS", "PARTICLE_UB", "DDPG",
+                                         "SAC_SHALLOW"};
+static_assert(sizeof(kKindNames) / sizeof(kKindNames[0]) == kNumKinds, "one name per kind");
+
+// A kind without a data-parallel step (DDPG, SAC_SHALLOW) is single-process:
+// its data-parallel entry points fail by name.
 static bool no_dp_step(const SacPlan& p, const char* entry) {
   if (kind_ops(p.c.kind).step_phase) return false;
-  set_error("%s: DDPG (kind %d) has no data-parallel step", entry, p.c.kind);
+  set_error("%s: %s (kind %d) has no data-parallel step", entry, kKindNames[p.c.kind], p.c.kind);
   return true;
 }
 
@@ -183,10 +192,34 @@ int oac_tuning_set(int key, int value) {
 
 static int validate(const oac_sac_config* c) {
   if (!c) { set_error("null config"); return 1; }
-  if (c->kind != OAC_KIND_SAC && c->kind != OAC_KIND_PARTICLE && c->kind != OAC_KIND_GAUSS &&
-      c->kind != OAC_KIND_PARTICLE_UB && c->kind != OAC_KIND_DDPG) {
+  if (c->kind < 0 || c->kind >= kNumKinds) {
     set_error("bad kind %d", c->kind);
     return 1;
+  }
+  if (c->kind == OAC_KIND_SAC_SHALLOW) {   // one-hidden-layer SAC / OAC: its own conditions, by name
+    const char* nm = kKindNames[c->kind];
+    if (c->n_hidden != 1) {
+      set_error("%s (kind %d): n_hidden must be 1 (one hidden layer), got %d; the two-layer "
+                "networks are OAC_KIND_SAC (kind %d)", nm, c->kind, c->n_hidden, OAC_KIND_SAC);
+      return 1;
+    }
+    if (c->q_out != 1) {
+      set_error("%s (kind %d) needs q_out == 1, got %d", nm, c->kind, c->q_out);
+      return 1;
+    }
+    if (c->world_size != 1) {
+      set_error("%s (kind %d) is single-process: world_size must be 1, got %d", nm, c->kind,
+                c->world_size);
+      return 1;
+    }
+    if (c->global_opt) {
+      set_error("%s (kind %d): global_opt must be 0, got %d", nm, c->kind, c->global_opt);
+      return 1;
+    }
+    if (c->unshared) {
+      set_error("%s (kind %d): unshared must be 0, got %d", nm, c->kind, c->unshared);
+      return 1;
+    }
   }
   if (c->kind == OAC_KIND_PARTICLE_UB &&
       (c->q_out < 2 || c->q_out > 16 || c->delta_index < 0 || c->delta_index >= c->q_out)) {
@@ -214,11 +247,12 @@ static int validate(const oac_sac_config* c) {
     set_error("n_hidden must be 1 or 2 (0 = 2), got %d", c->n_hidden);
     return 1;
   }
-  if (c->n_hidden == 1 && !has_target_policy(c->kind)) {
-    static const char* const names[] = {"SAC", "PARTICLE", "GAUSS", "PARTICLE_UB", "DDPG"};
+  if (c->n_hidden == 1 && !has_target_policy(c->kind) && c->kind != OAC_KIND_SAC_SHALLOW) {
     set_error("n_hidden = 1: kind %d (%s) has two-hidden-layer networks only; one hidden layer "
-              "is implemented for GAUSS (kind %d) and PARTICLE_UB (kind %d)",
-              c->kind, names[c->kind], OAC_KIND_GAUSS, OAC_KIND_PARTICLE_UB);
+              "is implemented for GAUSS (kind %d) and PARTICLE_UB (kind %d), and for the SAC / "
+              "OAC trainer as SAC_SHALLOW (kind %d)",
+              c->kind, kKindNames[c->kind], OAC_KIND_GAUSS, OAC_KIND_PARTICLE_UB,
+              OAC_KIND_SAC_SHALLOW);
     return 1;
   }
   if (c->n_hidden == 1 && (c->hidden & 3) && !c->unshared) {   // (unshared: its own message below)
@@ -231,10 +265,9 @@ static int validate(const oac_sac_config* c) {
     return 1;
   }
   if (c->global_opt && (!has_target_policy(c->kind) || c->world_size != 1)) {
-    static const char* const names[] = {"SAC", "PARTICLE", "GAUSS", "PARTICLE_UB", "DDPG"};
     set_error("global_opt: kind %d (%s) with world_size %d is not supported; the policy sweep is "
               "implemented for GAUSS (kind %d) and PARTICLE_UB (kind %d), single process",
-              c->kind, names[c->kind], c->world_size, OAC_KIND_GAUSS, OAC_KIND_PARTICLE_UB);
+              c->kind, kKindNames[c->kind], c->world_size, OAC_KIND_GAUSS, OAC_KIND_PARTICLE_UB);
     return 1;
   }
   if (c->unshared != 0 && c->unshared != 1) {
@@ -242,8 +275,7 @@ static int validate(const oac_sac_config* c) {
     return 1;
   }
   if (c->unshared) {   // share_layers=False: q_out stacked one-output critics (det_plan.hip)
-    static const char* const names[] = {"SAC", "PARTICLE", "GAUSS", "PARTICLE_UB", "DDPG"};
-    const char* nm = names[c->kind];
+    const char* nm = kKindNames[c->kind];
     if (!has_target_policy(c->kind)) {
       set_error("unshared: kind %d (%s) is not supported; separate critics are implemented for "
                 "GAUSS (kind %d, q_out == 2) and PARTICLE_UB (kind %d, 2 <= q_out <= 16)",
@@ -299,7 +331,7 @@ static void plan_splits(SacPlan& p) {
   const int tm = split_tile_m(p.cfg), tn = split_tile_n(p.cfg);
   auto tiles = [&](int M, int N) { return ((M + tm - 1) / tm) * ((N + tn - 1) / tn); };
   const int H = c.hidden, Dq = c.obs_dim + c.act_dim, Do = c.obs_dim, Da = c.act_dim;
-  const int nq = (c.kind == OAC_KIND_SAC) ? 2 : 1;
+  const int nq = twin_critics(c.kind) ? 2 : 1;
   p.sp_q1 = choose_split(c.batch, nq * (tiles(H, H + 1) + tiles(c.q_out, H + 1)), p.cfg);
   p.sp_ql = p.sp_q1;
   const int Hq = q_hidden(p);   // (unshared: the stacked critic block's width)
@@ -369,6 +401,13 @@ int oac_sac_create(const oac_sac_config* cfg, const oac_sac_buffers* bufs, oac_s
   p.c = *cfg;
   compute_layout(p.c, p.L);
   plan_splits(p);
+  if (p.c.kind == OAC_KIND_SAC_SHALLOW && p.cfg != 0) {   // (sac_shallow_plan.hip: small kernels only)
+    set_error("SAC_SHALLOW (kind %d): batch %d with gemm_cfg %d selects the large-batch kernel set "
+              "(cfg %d), which the one-hidden-layer SAC step does not have; use batch < 1024 or "
+              "gemm_cfg 0", p.c.kind, p.c.batch, p.c.gemm_cfg, p.cfg);
+    delete h;
+    return 1;
+  }
   kind_ops(p.c.kind).layout(p);
   p.b = *bufs;
   const int shadow = kind_ops(p.c.kind).shadow_ws;
@@ -409,8 +448,8 @@ int oac_sac_step_n(oac_sac* h, int flags, int n_steps, void* stream) {
   const KindOps& ops = kind_ops(p.c.kind);
   // (a kind without a data-parallel step issues direct launches only)
   if (!ops.step_phase && (flags & OAC_STEP_USE_GRAPH)) {
-    set_error("DDPG (kind %d): OAC_STEP_USE_GRAPH is not supported, issue the step's launches "
-              "directly", p.c.kind);
+    set_error("%s (kind %d): OAC_STEP_USE_GRAPH is not supported, issue the step's launches "
+              "directly", kKindNames[p.c.kind], p.c.kind);
     return 1;
   }
   if (p.c.global_opt && (flags & OAC_STEP_USE_GRAPH)) {
@@ -499,7 +538,8 @@ int oac_sac_set_host_ring(oac_sac* h, int32_t* pinned_ring) {
     p.owns_host_ring = true;
     // direct mode needs the small-batch kernel (cfg 0)
     p.rows_direct = p.cfg == 0 && !has_target_policy(p.c.kind) &&
-                    p.c.kind != OAC_KIND_PARTICLE &&   // sac_plan's phase0, ddpg_plan's forward
+                    p.c.kind != OAC_KIND_PARTICLE &&   // sac_plan's phase0, ddpg_plan's and
+                                                       // sac_shallow_plan's forward
                     p.c.row_stride / 4 <= 64 * 4;      // a side wave's row copy (gemm_small.hip)
     // (a direct large-batch step's 768 layer-0 tiles would each read their
     // rows' indices across the host link: its slot is copied to the device

@@ -1223,6 +1223,164 @@ __global__ void __launch_bounds__(256) ddpg_head_backward_kernel(DdpgHeadBwdArgs
   }
 }
 
+// --------------------------------------------------------------------------
+// SAC / OAC with one hidden layer (SacShallowTargetArgs, sac_shallow_plan.hip).
+// All six critic evaluations of the step use the pre-step weights
+// (trainer/trainer.py:151-180), so their width-1 last layers run here on the
+// hidden activations the layer-0 and head launches left, ahead of the critics'
+// Adam; then the two-layer step's row math (target_math.h), and the critics'
+// backward into their hidden layer by the whole block, as gauss_targets_kernel's.
+// 16 rows per block; every block redoes the 4-byte-per-row alpha reduction.
+// --------------------------------------------------------------------------
+__global__ void __launch_bounds__(256) sac_shallow_targets_kernel(SacShallowTargetArgs p) {
+  __shared__ RowHeadLds hs[QV_COUNT];
+  __shared__ float red[256];
+  __shared__ float sdq[2][kRowBlock];
+  const CriticTargetArgs& c = p.t;
+  const int B = c.B, t = threadIdx.x;
+  const int r0 = blockIdx.x * kRowBlock, r = r0 + t;
+  // the row's inputs first (clamped row), in flight across the heads
+  const int rc = min(r0 + (t & (kRowBlock - 1)), B - 1);
+  const float rew = c.batch[(long)rc * c.ld_batch + c.off_rew];
+  const float term = c.batch[(long)rc * c.ld_batch + c.off_term];
+  const float logp2 = c.logp2[rc];
+#pragma unroll
+  for (int k = 0; k < QV_COUNT; ++k) row_heads(p.head[k], 1, B, r0, hs[k]);
+  __syncthreads();
+  float alpha = 0.f;
+  if (c.alpha) {   // every block computes the update identically; block 0 publishes next_*
+    const float S = logp_sum256(c.logp1, B, c.target_entropy, red);
+    alpha = alpha_update(c, S, blockIdx.x == 0 && t == 0);
+  }
+  if (t < kRowBlock) {
+    float dq1 = 0.f, dq2 = 0.f;
+    if (r < B) {
+      TargetRowIn x;
+#pragma unroll
+      for (int k = 0; k < QV_COUNT; ++k) {
+        x.pb[k] = 0.f;
+#pragma unroll
+        for (int u = 0; u < 16; ++u) x.pv[k][u] = u == 0 ? hs[k].out[t][0] : 0.f;
+      }
+      x.rew = rew; x.term = term; x.logp2 = logp2;
+      target_row(c, r, x, alpha, true, dq1, dq2);
+    }
+    sdq[0][t] = dq1;
+    sdq[1][t] = dq2;
+  }
+  __syncthreads();
+  const int H = p.head[QV_Q1].H, n4 = H >> 2;
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {   // dh1q_i = [h1q_i > 0] dq_i (x) w_last_i
+    const RowHead& hd = p.head[i];
+    float* out = p.dh1q[i];
+    for (int e = t; e < kRowBlock * n4; e += 256) {
+      const int rr = e / n4, cc = 4 * (e - rr * n4), m = r0 + rr;
+      if (m >= B) continue;
+      const float4 h = *reinterpret_cast<const float4*>(hd.h + (long)m * H + cc);
+      const float4 w = *reinterpret_cast<const float4*>(hd.w + cc);
+      const float g = sdq[i][rr];
+      float4 o;
+      o.x = h.x > 0.f ? g * w.x : 0.f; o.y = h.y > 0.f ? g * w.y : 0.f;
+      o.z = h.z > 0.f ? g * w.z : 0.f; o.w = h.w > 0.f ? g * w.w : 0.f;
+      *reinterpret_cast<float4*>(out + (long)m * H + cc) = o;
+    }
+  }
+}
+
+// The policy loss's backward from the hidden layer of Q_i(obs, a~) to the
+// policy heads (SacShallowPolicyBwdArgs), det_seed_head_backward_kernel's
+// pattern: 16 rows per 256-thread block, 16 lanes per row; dh1n_i goes through
+// LDS in chunks of kDshChunk hidden units (lane l of a row computes units l,
+// l + 16, ...), then lane (phase, j) sums every nph-th unit of the chunk times
+// its action column j, critic 1's units then critic 2's in one chain, and the
+// phases are added by a fixed butterfly inside the row's 16 lanes.  No thread
+// leaves early: rows past B are clamped and only their stores are skipped.
+__global__ void __launch_bounds__(256)
+sac_shallow_policy_backward_kernel(SacShallowPolicyBwdArgs p) {
+  __shared__ float sdh[kRowBlock][kDshChunk + 1];
+  const int r0 = blockIdx.x * kRowBlock;
+  const int H = p.H, Da = p.Da, B = p.B;
+  const int row = threadIdx.x >> 4, l = threadIdx.x & 15;
+  const int m = min(r0 + row, B - 1);
+  // lanes of a row over (phase, action dim): Dp = the power of two >= min(Da, 16)
+  int Dp = 1;
+  while (Dp < Da && Dp < 16) Dp <<= 1;
+  const int nph = 16 / Dp, jl = l & (Dp - 1), ph = l / Dp;
+  const int j0 = min(jl, Da - 1), j1 = min(jl + 16, Da - 1);   // (Da > 16: two dims per lane)
+  float acc0 = 0.f, acc1 = 0.f;
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const float* h1 = p.h1n[i] + (long)m * H;
+    const float* wl = p.wl[i];
+    const float* wa = p.wa[i];
+    const float g = p.gq[i][m];
+    for (int c0 = 0; c0 < H; c0 += kDshChunk) {
+      const int nc = min(kDshChunk, H - c0);
+      for (int k = l; k < nc; k += 16) {
+        const int n = c0 + k;
+        sdh[row][k] = h1[n] > 0.f ? g * wl[n] : 0.f;
+      }
+      __syncthreads();
+      for (int k = ph; k < nc; k += nph) {
+        const float d = sdh[row][k];
+        const float* w = wa + (long)(c0 + k) * p.ld_wa;
+        acc0 = fmaf(d, w[j0], acc0);
+        acc1 = fmaf(d, w[j1], acc1);
+      }
+      __syncthreads();
+    }
+  }
+  for (int off = Dp; off < 16; off <<= 1) {
+    acc0 += __shfl_xor(acc0, off, 64);
+    acc1 += __shfl_xor(acc1, off, 64);
+  }
+  if (r0 + row >= B || ph != 0) return;
+  const float alpha = p.alpha ? p.alpha->alpha : 0.f;
+  const float G = alpha * (1.f / (float)B);
+  const float* hd = p.head + (long)m * 2 * Da;
+  float* dh = p.dhead + (long)m * 2 * Da;
+  if (jl < Da) {
+    const long e = (long)m * Da + jl;
+    float dmean, dls;
+    tanh_gauss_backward(acc0, p.act[e], p.stdv[e], p.u[e], p.eps[e], hd[Da + jl], G, dmean, dls);
+    dh[jl] = dmean;
+    dh[Da + jl] = dls;
+  }
+  if (jl + 16 < Da) {
+    const long e = (long)m * Da + jl + 16;
+    float dmean, dls;
+    tanh_gauss_backward(acc1, p.act[e], p.stdv[e], p.u[e], p.eps[e], hd[Da + jl + 16], G, dmean, dls);
+    dh[jl + 16] = dmean;
+    dh[Da + jl + 16] = dls;
+  }
+}
+
+hipError_t launch_sac_shallow_targets(const SacShallowTargetArgs& a, hipStream_t s) {
+  const CriticTargetArgs& c = a.t;
+  if (c.B < 1 || c.n_part != 0 || c.world_size > 1 || c.wl_h2[0] || !c.batch || !c.logp2 || !c.state ||
+      !c.y || !c.dq1 || !c.dq2 || !c.gq1 || !c.gq2 || !c.sqe1 || !c.sqe2 || !c.qnew ||
+      (c.alpha && !c.logp1) || !a.dh1q[0] || !a.dh1q[1])
+    return hipErrorInvalidValue;
+  for (int k = 0; k < QV_COUNT; ++k)
+    if (!a.head[k].h || !head_ok(a.head[k]) || a.head[k].seg || a.head[k].H != a.head[0].H ||
+        a.head[k].out != c.q[k])
+      return hipErrorInvalidValue;
+  if (a.head[0].H & 3) return hipErrorInvalidValue;   // float4 columns of dh1q
+  OAC_LAUNCH(sac_shallow_targets_kernel, dim3((c.B + kRowBlock - 1) / kRowBlock), dim3(256), 0, s, a);
+  return hipGetLastError();
+}
+hipError_t launch_sac_shallow_policy_backward(const SacShallowPolicyBwdArgs& a, hipStream_t s) {
+  if (a.B < 1 || a.H < 1 || a.Da < 1 || a.Da > 32 || !a.act || !a.stdv || !a.u || !a.eps || !a.head ||
+      !a.dhead)
+    return hipErrorInvalidValue;
+  for (int i = 0; i < 2; ++i)
+    if (!a.h1n[i] || !a.gq[i] || !a.wl[i] || !a.wa[i]) return hipErrorInvalidValue;
+  OAC_LAUNCH(sac_shallow_policy_backward_kernel, dim3((a.B + kRowBlock - 1) / kRowBlock), dim3(256), 0,
+             s, a);
+  return hipGetLastError();
+}
+
 hipError_t launch_ddpg_targets(const DdpgTargetArgs& a, hipStream_t s) {
   if (!a.qh.h || !a.th.h || !a.nh.h || !head_ok(a.qh) || !head_ok(a.th) || !head_ok(a.nh) || a.B < 1)
     return hipErrorInvalidValue;

@@ -460,6 +460,9 @@ inline int dp_step_phase(SacPlan& p, int phase, hipStream_t s, F0 phase0, F1 pha
 inline bool has_target_policy(int kind) {
   return kind == OAC_KIND_GAUSS || kind == OAC_KIND_PARTICLE_UB;
 }
+// the SAC / OAC trainer's twin critics, at either depth
+inline bool twin_critics(int kind) { return kind == OAC_KIND_SAC || kind == OAC_KIND_SAC_SHALLOW; }
+constexpr int kNumKinds = OAC_KIND_SAC_SHALLOW + 1;
 
 // ---------------------------------------------------------------- kinds
 // What the C ABI (plan_api.hip) needs of a trainer kind: one table entry.
@@ -497,5 +500,10 @@ void ddpg_layout_workspace(SacPlan& p);
 int ddpg_run_step(SacPlan& p, int flags, hipStream_t s, int i, int n);
 int ddpg_ws_alias(int which);
 int ddpg_shadow_ws();
+// SAC / OAC with one hidden layer (sac_shallow_plan.hip); single-process,
+// small-batch kernel set only
+void sac_shallow_layout_workspace(SacPlan& p);
+int sac_shallow_run_step(SacPlan& p, int flags, hipStream_t s, int i, int n);
+int sac_shallow_ws_alias(int which);
 
 }  // namespace oac

@@ -1,7 +1,8 @@
 """oac_amd -- MI355X-native OAC/SAC gradient-step hot path.
 
 Drop-in replacements for the reference's hot-path interfaces:
-  SACTrainer                         trainer/trainer.py
+  SACTrainer                         trainer/trainer.py (--num_layers 2)
+  ShallowSACTrainer                  trainer/trainer.py at one hidden layer (--num_layers 1)
   ParticleTrainer                    trainer/particle_trainer.py (p-oac recipes; share_layers,
                                      or separate critics at one hidden layer)
   ParticleTrainerOAC                 trainer/particle_trainer_oac.py (share_layers)
@@ -14,7 +15,7 @@ Drop-in replacements for the reference's hot-path interfaces:
 backed by liboac_amd.so (hand-written HIP for gfx950 behind a C ABI).
 """
 from ._lib import lib, LIB_PATH  # noqa: F401
-from .trainer import SACTrainer, row_layout  # noqa: F401
+from .trainer import SACTrainer, ShallowSACTrainer, row_layout  # noqa: F401
 from .particle_trainer import ParticleTrainer  # noqa: F401
 from .particle_trainer_oac import ParticleTrainer as ParticleTrainerOAC  # noqa: F401
 from .gaussian_trainer import GaussianTrainer  # noqa: F401

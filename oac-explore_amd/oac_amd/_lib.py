@@ -18,6 +18,7 @@ OAC_KIND_PARTICLE = 1
 OAC_KIND_GAUSS = 2
 OAC_KIND_PARTICLE_UB = 3
 OAC_KIND_DDPG = 4
+OAC_KIND_SAC_SHALLOW = 5
 
 OAC_STEP_GATHER = 1
 OAC_STEP_DEVICE_EPS = 2
@@ -233,6 +234,10 @@ _SIGS = {
                                              ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                              ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
                                              ctypes.POINTER(ctypes.c_void_p)]),
+    "oac_expl_create_shallow": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                               ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                               ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
+                                               ctypes.POINTER(ctypes.c_void_p)]),
     "oac_expl_create_shared": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                               ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
                                               ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,

@@ -1,7 +1,7 @@
 """Drop-in ``get_optimistic_exploration_action``
 (/root/reference/optimistic_exploration.py:7-11) -- the OAC action shift,
 computed by liboac_amd in one launch (csrc/expl_plan.hip, expl_split.hip), for
-twin critics (SACTrainer) or one shared-layer critic with K heads
+twin critics (SACTrainer; ShallowSACTrainer: csrc/expl_shallow.hip) or one shared-layer critic with K heads
 (ParticleTrainerOAC, share_layers: Q_UB = mean_k + beta_UB std_k).
 
 Same signature and return value as the reference: ``(action float32[Da], {})``

@@ -57,7 +57,8 @@ def _dims_from_state(pol_sd, q_sd, fixed_std=False, depths=(2,)):
     if dp not in depths:
         raise ValueError(f"liboac_amd implements the 2-hidden-layer MLPs of the reference "
                          f"recipes (layer_size x 2), and 1-hidden-layer MLPs (--num_layers 1) "
-                         f"for GaussianTrainer and ParticleTrainer only; got {dp} hidden layers")
+                         f"for GaussianTrainer and ParticleTrainer only; got {dp} hidden layers "
+                         f"(the SAC / OAC trainer at one hidden layer is ShallowSACTrainer)")
     H, Do = pol_sd["fc0.weight"].shape
     Da = pol_sd["last_fc.weight"].shape[0]
     if q_sd["fc0.weight"].shape != (H, Do + Da) or \
@@ -153,7 +154,7 @@ class _ArenaTrainer(object):
 
     _kind = _lib.OAC_KIND_SAC
     _q_out = 1
-    n_hidden = 2   # hidden layers of the policy and the critic (1: the det trainers only)
+    n_hidden = 2   # hidden layers of the policy and the critic (1: the det trainers, ShallowSACTrainer)
 
     def _alloc(self, Do, Da, H, device):
         L = _lib.lib()
@@ -434,12 +435,13 @@ class _ArenaTrainer(object):
             h = ctypes.c_void_p()
             p = self.params
             q1 = ctypes.c_void_p(p.data_ptr() + 4 * self.layout.q1_base)
-            if self.layout.q2_base >= 0:     # twin critics
-                check(L.oac_expl_create_batch(n, self.obs_dim, self.act_dim, self.hidden, ptr(p),
-                                              q1,
-                                              ctypes.c_void_p(p.data_ptr() + 4 * self.layout.q2_base),
-                                              ptr(ws), ptr(self.step_state),
-                                              ctypes.c_uint64(self.seed + 1), ctypes.byref(h)))
+            if self.layout.q2_base >= 0:     # twin critics (one hidden layer: a kernel of its own)
+                create = (L.oac_expl_create_shallow if self.n_hidden == 1
+                          else L.oac_expl_create_batch)
+                check(create(n, self.obs_dim, self.act_dim, self.hidden, ptr(p), q1,
+                             ctypes.c_void_p(p.data_ptr() + 4 * self.layout.q2_base),
+                             ptr(ws), ptr(self.step_state),
+                             ctypes.c_uint64(self.seed + 1), ctypes.byref(h)))
             else:                            # one shared-layer critic with K heads
                 check(L.oac_expl_create_shared(n, self.obs_dim, self.act_dim, self.hidden,
                                                self._q_out, ptr(p), q1, ptr(ws),
@@ -494,7 +496,7 @@ class SACTrainer(_ArenaTrainer):
         ref_pol = policy_producer()
         ref_q = [q_producer() for _ in range(4)]   # qf1, qf2, target_qf1, target_qf2
         pol_sd = {k: v.detach() for k, v in ref_pol.state_dict().items()}
-        Do, Da, H, Q = _dims_from_state(pol_sd, ref_q[0].state_dict())
+        Do, Da, H, Q = self._read_dims(pol_sd, ref_q[0].state_dict())
         if Q != 1:
             raise ValueError("SACTrainer critics have one output")
         lay = self._alloc(Do, Da, H, self.device)
@@ -526,6 +528,10 @@ class SACTrainer(_ArenaTrainer):
         self.eval_statistics = OrderedDict()
         self._n_train_steps_total = 0
         self._need_to_update_eval_statistics = True
+
+    def _read_dims(self, pol_sd, q_sd):
+        """(Do, Da, H, Q) of the producers' networks, at the depth this class takes."""
+        return _dims_from_state(pol_sd, q_sd)
 
     # ------------------------------------------------------------ diagnostics
     def _fill_eval_statistics(self, plan):
@@ -621,3 +627,46 @@ class SACTrainer(_ArenaTrainer):
         self.step_state[0] = self._n_train_steps_total
 
     # ------------------------------------------------------------ exploration
+
+
+class ShallowSACTrainer(SACTrainer):
+    """SACTrainer (trainer/trainer.py:14) with one-hidden-layer networks:
+    main.py's ``--num_layers 1`` default (oac.sh, sac.sh, the lqg lines of
+    reproduce.sh).  Same constructor, statistics, ``networks`` and snapshots as
+    ``SACTrainer``; the arena modules register ``fc0``, ``last_fc`` and
+    ``last_fc_log_std`` only, so the reference's depth-1 checkpoints load.  The
+    step is liboac_amd's OAC_KIND_SAC_SHALLOW plan (csrc/sac_shallow_plan.hip)
+    and ``get_optimistic_exploration_action`` on its policy and critics runs
+    csrc/expl_shallow.hip.  Single process, small-batch kernel set (batch <
+    1024), direct launches: ``use_graph=True`` is not implemented."""
+
+    _kind = _lib.OAC_KIND_SAC_SHALLOW
+    n_hidden = 1
+
+    def __init__(self, policy_producer, q_producer, action_space=None, discount=0.99,
+                 reward_scale=1.0, policy_lr=1e-3, qf_lr=1e-3, optimizer_class=None,
+                 soft_target_tau=1e-2, target_update_period=1,
+                 use_automatic_entropy_tuning=True, target_entropy=None, deterministic=False,
+                 device=None, seed=0, use_graph=False, gemm_cfg=-1):
+        if use_graph:
+            raise NotImplementedError(
+                "ShallowSACTrainer: use_graph=True is not implemented (the one-hidden-layer "
+                "step issues its launches directly); SACTrainer (two hidden layers) has it")
+        super().__init__(policy_producer, q_producer, action_space=action_space, discount=discount,
+                         reward_scale=reward_scale, policy_lr=policy_lr, qf_lr=qf_lr,
+                         optimizer_class=optimizer_class, soft_target_tau=soft_target_tau,
+                         target_update_period=target_update_period,
+                         use_automatic_entropy_tuning=use_automatic_entropy_tuning,
+                         target_entropy=target_entropy, deterministic=deterministic, device=device,
+                         seed=seed, use_graph=False, gemm_cfg=gemm_cfg)
+
+    def _read_dims(self, pol_sd, q_sd):
+        dp, dq = _depth(pol_sd), _depth(q_sd)
+        if dp == dq and dp != 1:
+            raise ValueError(f"ShallowSACTrainer takes the 1-hidden-layer MLPs of --num_layers 1; "
+                             f"got {dp} hidden layers (two hidden layers: SACTrainer)")
+        dims = _dims_from_state(pol_sd, q_sd, depths=(1,))
+        if dims[2] % 4:
+            raise ValueError(f"ShallowSACTrainer: the hidden width must be a multiple of 4 (the row "
+                             f"kernels read the hidden activations as float4 columns), got {dims[2]}")
+        return dims
