@@ -504,6 +504,13 @@ int oac_expl_set_ub_index(oac_expl* h, int index);
  * [2*act_dim, hidden] head).  offsets[2] = -1 (a depth-1 layout's fc1 fields;
  * offsets[3] is then not read): a one-hidden-layer network, the last layer and
  * the Jacobian start from layer 0's activations.
+ * A workgroup keeps its row in dynamic LDS: (obs_dim + act_dim + 4*hidden +
+ * q_out + 4) floats for a critic, (obs_dim + 2*hidden + 3*act_dim + 4) for a
+ * policy, 2*act_dim + 2 more with a fixed std.  Each entry point admits exactly
+ * the request its launch makes, up to 160 KiB, and refuses a larger one with
+ * "dims exceed the workgroup's LDS" before any launch.  Requests past 64 KiB
+ * need no hipFuncSetAttribute call on this runtime (measured at 65,636 and
+ * 163,840 bytes on an MI355X), so none is made.
  * oac_critic_eval: FlattenMlp(obs, act) (networks.py:154-161) of n_nets (1 or 2)
  * critic blocks -> q [n, n_nets*q_out]; jac (optional) [n, n_nets*q_out,
  * obs_dim+act_dim] = d q / d [obs | act], for SACTrainer.predict /

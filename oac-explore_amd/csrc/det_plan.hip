@@ -430,6 +430,7 @@ static int dphase2(SacPlan& p, hipStream_t s, bool fused) {
 int det_run_step(SacPlan& p, int flags, hipStream_t s, int, int) {
   p.launches = 0;
   const bool fused = can_fuse_adam(p);
+  if (fused) p.trace |= OAC_TRACE_FUSED;
   if (dphase0(p, flags, s)) return 1;
   if (dphase1(p, flags, s, fused)) return 1;
   // (unshared: phase 1's last launch has stepped the critic block)

@@ -180,6 +180,10 @@ __global__ void __launch_bounds__(256) policy_eval_kernel(MlpEvalArgs a) {
   }
 }
 
+// the dynamic LDS a workgroup of gfx950 may hold: every entry point below
+// admits exactly the requests mlp_eval_lds_bytes makes up to this figure
+constexpr size_t kMlpEvalMaxLds = 160 * 1024;
+
 size_t mlp_eval_lds_bytes(const MlpEvalArgs& a, bool policy) {
   const int din = a.d0 + a.d1;
   // (policy: + Q doubles-as-floats for the fixed-std log-prob terms, 8-byte aligned)
@@ -212,10 +216,6 @@ extern "C" int oac_critic_eval(const float* const* nets, int n_nets, const int64
     set_error("critic eval: bad arguments");
     return 1;
   }
-  if ((size_t)(obs_dim + act_dim + 4 * hidden + q_out) * 4 > 160 * 1024) {
-    set_error("critic eval: dims exceed the workgroup's LDS");
-    return 1;
-  }
   MlpEvalArgs a;
   memset(&a, 0, sizeof(a));
   for (int i = 0; i < n_nets; ++i) a.net[i] = nets[i];
@@ -226,6 +226,10 @@ extern "C" int oac_critic_eval(const float* const* nets, int n_nets, const int64
   a.x1 = act; a.ld_x1 = ld_act; a.d1 = act_dim;
   a.H = hidden; a.Q = q_out; a.N = n;
   a.out = q_out_buf; a.ld_out = (long)n_nets * q_out; a.jac = jac;
+  if (mlp_eval_lds_bytes(a, false) > kMlpEvalMaxLds) {
+    set_error("critic eval: dims exceed the workgroup's LDS");
+    return 1;
+  }
   OAC_HIP_CHECK(launch_critic_eval(a, reinterpret_cast<hipStream_t>(stream)));
   return 0;
 }
@@ -239,10 +243,6 @@ extern "C" int oac_policy_eval(const float* net, const int64_t* offsets, int obs
     set_error("policy eval: bad arguments");
     return 1;
   }
-  if ((size_t)(obs_dim + 2 * hidden + 3 * act_dim + 4) * 4 > 160 * 1024) {
-    set_error("policy eval: dims exceed the workgroup's LDS");
-    return 1;
-  }
   MlpEvalArgs a;
   memset(&a, 0, sizeof(a));
   a.net[0] = net; a.n_nets = 1;
@@ -252,6 +252,10 @@ extern "C" int oac_policy_eval(const float* net, const int64_t* offsets, int obs
   a.H = hidden; a.Q = 2 * act_dim; a.N = n;
   a.p_eps = eps; a.p_action = action; a.p_mean = mean; a.p_log_std = log_std;
   a.p_log_prob = log_prob; a.p_std = std_out; a.p_pre_tanh = pre_tanh;
+  if (mlp_eval_lds_bytes(a, true) > kMlpEvalMaxLds) {
+    set_error("policy eval: dims exceed the workgroup's LDS");
+    return 1;
+  }
   OAC_HIP_CHECK(launch_policy_eval(a, reinterpret_cast<hipStream_t>(stream)));
   return 0;
 }
@@ -266,10 +270,6 @@ extern "C" int oac_policy_eval_fixed_std(const float* net, const int64_t* offset
     set_error("policy eval (fixed std): bad arguments");
     return 1;
   }
-  if ((size_t)(obs_dim + 2 * hidden + 5 * act_dim + 8) * 4 > 160 * 1024) {
-    set_error("policy eval (fixed std): dims exceed the workgroup's LDS");
-    return 1;
-  }
   MlpEvalArgs a;
   memset(&a, 0, sizeof(a));
   a.net[0] = net; a.n_nets = 1;
@@ -280,6 +280,10 @@ extern "C" int oac_policy_eval_fixed_std(const float* net, const int64_t* offset
   a.p_eps = eps; a.p_action = action; a.p_mean = mean; a.p_log_std = log_std;
   a.p_log_prob = log_prob; a.p_std = std_out; a.p_pre_tanh = pre_tanh;
   a.p_fixed_std = std_dev;
+  if (mlp_eval_lds_bytes(a, true) > kMlpEvalMaxLds) {
+    set_error("policy eval (fixed std): dims exceed the workgroup's LDS");
+    return 1;
+  }
   OAC_HIP_CHECK(launch_policy_eval(a, reinterpret_cast<hipStream_t>(stream)));
   return 0;
 }

@@ -139,6 +139,95 @@ def load_mid_state(tr, ms):
     tr.step_state[0] = ms["t"]
 
 
+# ------------------------------------------------- oracle from own state
+def _np_sd(mod):
+    return {k: v.detach().cpu().numpy().copy() for k, v in mod.state_dict().items()}
+
+
+def oracle_from(tr, meta, dtype):
+    """The CPU oracle holding the trainer's current state (parameters, targets,
+    Adam moments and step count, log-alpha and its Adam state)."""
+    from gpu_helpers import module_tensors
+    from oracle import sac_oracle as so
+    params = {g: _np_sd(getattr(tr, g)) for g in GROUPS + TARGETS}
+    orc = so.SACOracle(params, meta["obs_dim"], meta["act_dim"], discount=meta["discount"],
+                       reward_scale=meta["reward_scale"], policy_lr=meta["lr"], qf_lr=meta["lr"],
+                       tau=meta["tau"], auto_alpha=meta["auto_alpha"],
+                       target_update_period=meta.get("target_update_period", 1), dtype=dtype)
+    t = tr._n_train_steps_total
+    for opt, mod in ((orc.opt_p, tr.policy), (orc.opt_q1, tr.qf1), (orc.opt_q2, tr.qf2)):
+        m, v = module_tensors(tr, mod, tr.adam_m), module_tensors(tr, mod, tr.adam_v)
+        for k in opt.m:
+            opt.m[k].copy_(m[k].detach().cpu().to(dtype))
+            opt.v[k].copy_(v[k].detach().cpu().to(dtype))
+        opt.t = t
+    a = tr.alpha_state.detach().cpu().to(dtype)
+    orc.log_alpha.copy_(a[0:1])
+    orc.opt_a.m["log_alpha"].copy_(a[1:2])
+    orc.opt_a.v["log_alpha"].copy_(a[2:3])
+    orc.opt_a.t = t
+    orc.n_steps = t
+    return orc
+
+
+def oracle_tensors(meta, orc, out):
+    rec = {}
+    for grp, params, opt in _groups(orc):
+        for pn in params:
+            rec[f"grad/{grp}/{pn}"] = out["grads"][grp][pn].double().numpy().copy()
+            rec[f"post/{grp}/{pn}"] = params[pn].double().numpy().copy()
+            rec[f"adam/{grp}/{pn}/exp_avg"] = opt.m[pn].double().numpy().copy()
+            rec[f"adam/{grp}/{pn}/exp_avg_sq"] = opt.v[pn].double().numpy().copy()
+    for grp, params in (("target_qf1", orc.T1), ("target_qf2", orc.T2)):
+        for pn, t in params.items():
+            rec[f"post/{grp}/{pn}"] = t.double().numpy().copy()
+    if meta["auto_alpha"]:
+        rec["grad/log_alpha"] = out["grads"]["log_alpha"].double().numpy().copy()
+        rec["post/log_alpha"] = orc.log_alpha.double().numpy().copy()
+    return rec
+
+
+def gpu_tensors(meta, tr):
+    from gpu_helpers import module_tensors
+    rec = {}
+    for grp in GROUPS:
+        mod = getattr(tr, grp)
+        for what, arena in (("grad", tr.grads), ("post", tr.params)):
+            for pn, t in module_tensors(tr, mod, arena).items():
+                rec[f"{what}/{grp}/{pn}"] = t.cpu().numpy()
+        m, v = module_tensors(tr, mod, tr.adam_m), module_tensors(tr, mod, tr.adam_v)
+        for pn in m:
+            rec[f"adam/{grp}/{pn}/exp_avg"] = m[pn].cpu().numpy()
+            rec[f"adam/{grp}/{pn}/exp_avg_sq"] = v[pn].cpu().numpy()
+    for grp in TARGETS:
+        for pn, t in getattr(tr, grp).state_dict().items():
+            rec[f"post/{grp}/{pn}"] = t.cpu().numpy()
+    if meta["auto_alpha"]:
+        a = tr.alpha_state.cpu().numpy()
+        rec["grad/log_alpha"], rec["post/log_alpha"] = a[5:6].copy(), a[0:1].copy()
+    return rec
+
+
+def step_against_oracle(tr, meta, batch, eps1, eps2, what):
+    """One step of the trainer and of the fp32 oracle from the trainer's own
+    pre-step state; {key: (error, gate)} for every tensor over its gate.  The
+    gate: 1e-5, or 3x the fp32 oracle's distance from the float64 oracle run
+    from the same state on the same inputs."""
+    o32, o64 = oracle_from(tr, meta, torch.float32), oracle_from(tr, meta, torch.float64)
+    tr.train_from_torch(batch, eps1=eps1, eps2=eps2)
+    torch.cuda.synchronize()
+    r32 = oracle_tensors(meta, o32, o32.step(batch, eps1, eps2))
+    r64 = oracle_tensors(meta, o64, o64.step(batch, eps1, eps2))
+    got = gpu_tensors(meta, tr)
+    assert sorted(got) == sorted(r32)
+    errs = {k: parity.rel_err(got[k], r32[k]) for k in r32}
+    gates = {k: parity.gate(k, parity.rel_err(r32[k], r64[k])) for k in r32}
+    w = max(errs, key=lambda k: errs[k] / gates[k])
+    print(f"{what}: worst {w} {errs[w]:.2e} (gate {gates[w]:.2e}), {errs[w] / gates[w]:.3f} of it; "
+          f"widest gate {max(gates.values()):.2e}")
+    return {k: (errs[k], gates[k]) for k in errs if not errs[k] <= gates[k]}
+
+
 def trainer_record(meta, g, tr):
     """The trainer's run of the fixture's steps (eps given), keyed like
     oracle_record's; the statistics' keys are checked against the reference's order."""

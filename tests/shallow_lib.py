@@ -122,3 +122,89 @@ def load_tpn(tr, g):
     """use_target_policy fixtures: the recorded target network's weights."""
     tr.target_policy_network.load_state_dict(
         {k[4:]: torch.as_tensor(np.asarray(v)) for k, v in g.items() if k.startswith("tpn/")})
+
+
+# ------------------------------------------- mid-training state, own-state oracle
+LOG_STD_HEAD = ("last_fc_log_std.weight", "last_fc_log_std.bias")
+
+
+def det_mid_state(groups, t, seed):
+    """fixtures_lib.mid_state for the deterministic-policy trainers: ``groups``
+    = {name: parameter dict} (policy, target_policy and each critic).  The
+    log-std heads never get a gradient, so torch's Adam keeps no state for them
+    (and the step leaves them bit-untouched): their moments stay zero."""
+    from fixtures_lib import mid_state
+    ms = mid_state(groups, list(groups), t, seed)
+    for grp in groups:
+        for pn in LOG_STD_HEAD:
+            if pn in ms[grp]:
+                m, v = ms[grp][pn]
+                ms[grp][pn] = (np.zeros_like(m), np.zeros_like(v))
+    return ms
+
+
+def load_mid_state(tr, mods, ms):
+    """det_mid_state into a GaussianTrainer / ParticleTrainer (shared or
+    separate critics): ``mods`` = {group name: arena module}."""
+    from gpu_helpers import module_tensors
+    for grp, mod in mods.items():
+        m, v = module_tensors(tr, mod, tr.adam_m), module_tensors(tr, mod, tr.adam_v)
+        for pn, (mm, vv) in ms[grp].items():
+            m[pn].copy_(torch.from_numpy(mm).reshape(m[pn].shape))
+            v[pn].copy_(torch.from_numpy(vv).reshape(v[pn].shape))
+    tr._n_train_steps_total = ms["t"]
+    tr.step_state[0] = ms["t"]
+
+
+def load_oracle_mid_state(orc, opts, ms):
+    """det_mid_state into a CPU oracle: ``opts`` = {group name: its Adam14}."""
+    for grp, opt in opts.items():
+        for pn, (m, v) in ms[grp].items():
+            opt.m[pn].copy_(torch.from_numpy(m).to(opt.m[pn].dtype))
+            opt.v[pn].copy_(torch.from_numpy(v).to(opt.v[pn].dtype))
+        opt.t = ms["t"]
+    orc.n_steps = ms["t"]
+
+
+def oracle_from_gpu(tr, meta, dtype=torch.float32):
+    """The shared-layer oracle holding the GPU trainer's current state
+    (parameters, targets, Adam moments and step count)."""
+    from gpu_helpers import module_tensors
+    torch.cuda.synchronize()
+    sd = lambda mod: {k: v.detach().cpu().numpy().copy() for k, v in mod.state_dict().items()}
+    qf, tf = critic_of(tr)
+    params = dict(policy=sd(tr.policy), target_policy=sd(tr.target_policy), qf1=sd(qf),
+                  target_qf1=sd(tf))
+    orc = make_oracle(meta, dtype, params=params)
+    for opt, mod in ((orc.opt_p, tr.policy), (orc.opt_tp, tr.target_policy), (orc.opt_q, qf)):
+        m, v = module_tensors(tr, mod, tr.adam_m), module_tensors(tr, mod, tr.adam_v)
+        for k in opt.m:
+            opt.m[k].copy_(m[k].detach().cpu())
+            opt.v[k].copy_(v[k].detach().cpu())
+        opt.t = tr._n_train_steps_total
+    orc.n_steps = tr._n_train_steps_total
+    return orc
+
+
+def step_tensors(orc, out, tr=None):
+    """{key: float64 array} of a shared-layer step just taken -- every
+    gradient, post-step parameter, Adam moment and the Polyak target, whole:
+    the oracle's (``tr`` None) or the GPU trainer's."""
+    from gpu_helpers import module_tensors
+    rec = {}
+    cpu = lambda t: t.detach().cpu().double().numpy().copy()
+    qf, tf = critic_of(tr) if tr is not None else (None, None)
+    for grp, want, opt, mod in (("policy", orc.P, orc.opt_p, getattr(tr, "policy", None)),
+                                ("target_policy", orc.TP, orc.opt_tp, getattr(tr, "target_policy", None)),
+                                ("qf", orc.Q, orc.opt_q, qf)):
+        if tr is not None:
+            srcs = (module_tensors(tr, mod, tr.grads), mod.state_dict(),
+                    module_tensors(tr, mod, tr.adam_m), module_tensors(tr, mod, tr.adam_v))
+        else:
+            srcs = (out["grads"][grp], want, opt.m, opt.v)
+        for pn in want:
+            for what, src in zip(("grad", "post", "adam_m", "adam_v"), srcs):
+                rec[f"{what}/{grp}/{pn}"] = cpu(src[pn])
+    for pn, t in (tf.state_dict() if tr is not None else orc.T).items():
+        rec[f"post/tf/{pn}"] = cpu(t)
+    return rec

@@ -153,3 +153,36 @@ def test_trace_bits_match_the_header():
     bits = {n[len("OAC_TRACE_"):].lower(): int(v)
             for n, v in re.findall(r"#define\s+(OAC_TRACE_[A-Z0-9_]+)\s+(\d+)", src)}
     assert bits == _lib.TRACE
+
+
+def test_eval_entry_points_refuse_one_float_past_the_lds_limit_by_name():
+    """oac_critic_eval / oac_policy_eval / oac_policy_eval_fixed_std admit
+    exactly the dynamic LDS their launch requests (csrc/mlp_eval.hip
+    mlp_eval_lds_bytes: critic (din + 4 H + Q + 4) floats, policy (Do + 2 H +
+    3 Da + 4), fixed std 2 Da + 2 more) up to 160 KiB = 40,960 floats: dims at
+    the limit pass (n = 0: no launch), one float more is refused with the
+    named message before any launch (host-only: the buffers are never read)."""
+    from oac_amd import _lib
+    L = _lib.lib()
+    buf = (ctypes.c_float * 4)()
+    p = ctypes.cast(buf, ctypes.c_void_p)
+    nets = (ctypes.c_void_p * 2)(p, p)
+    offs = (ctypes.c_int64 * 6)(0, 0, -1, 0, 0, 0)
+
+    def critic(Do, n):
+        return L.oac_critic_eval(nets, 1, offs, Do, 1, 10236, 1, p, Do, p, 1, n, p, p, None)
+
+    def policy(Do, n):
+        return L.oac_policy_eval(p, offs, Do, 1, 20000, p, Do, n, p, p, p, p, p, p, p, None)
+
+    def fixed(Do, n):
+        return L.oac_policy_eval_fixed_std(p, offs, Do, 1, 20000, p, Do, n, p, p, p, p, p, p, p, p,
+                                           None)
+
+    for call, Do, floats, name in ((critic, 10, 10 + 1 + 4 * 10236 + 1 + 4, b"critic eval"),
+                                   (policy, 953, 953 + 2 * 20000 + 3 + 4, b"policy eval"),
+                                   (fixed, 949, 949 + 2 * 20000 + 5 + 6, b"policy eval (fixed std)")):
+        assert floats == 40960
+        assert call(Do, 0) == 0, L.oac_last_error()
+        assert call(Do + 1, 1) != 0
+        assert name + b": dims exceed the workgroup's LDS" in L.oac_last_error()

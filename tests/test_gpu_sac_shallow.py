@@ -20,8 +20,7 @@ import parity
 import sac_shallow_lib as ssl
 import test_oracle_golden as tog
 from fixtures_lib import sac_params, synthetic_transitions
-from gpu_helpers import Space, StateDictModule, batch_from, module_tensors, producers, sac_trainer_for
-from oracle import sac_oracle as so
+from gpu_helpers import Space, StateDictModule, batch_from, producers, sac_trainer_for
 from oracle.philox_oracle import philox_normal
 
 pytestmark = pytest.mark.gpu
@@ -46,89 +45,9 @@ def test_step_matches_reference_golden(name):
 
 
 # ------------------------------------------------- oracle from own state
-def _np_sd(mod):
-    return {k: v.detach().cpu().numpy().copy() for k, v in mod.state_dict().items()}
-
-
-def _oracle_from(tr, meta, dtype):
-    """The CPU oracle holding the trainer's current state (parameters, targets,
-    Adam moments and step count, log-alpha and its Adam state)."""
-    params = {g: _np_sd(getattr(tr, g)) for g in ssl.GROUPS + ssl.TARGETS}
-    orc = so.SACOracle(params, meta["obs_dim"], meta["act_dim"], discount=meta["discount"],
-                       reward_scale=meta["reward_scale"], policy_lr=meta["lr"], qf_lr=meta["lr"],
-                       tau=meta["tau"], auto_alpha=meta["auto_alpha"],
-                       target_update_period=meta.get("target_update_period", 1), dtype=dtype)
-    t = tr._n_train_steps_total
-    for opt, mod in ((orc.opt_p, tr.policy), (orc.opt_q1, tr.qf1), (orc.opt_q2, tr.qf2)):
-        m, v = module_tensors(tr, mod, tr.adam_m), module_tensors(tr, mod, tr.adam_v)
-        for k in opt.m:
-            opt.m[k].copy_(m[k].detach().cpu().to(dtype))
-            opt.v[k].copy_(v[k].detach().cpu().to(dtype))
-        opt.t = t
-    a = tr.alpha_state.detach().cpu().to(dtype)
-    orc.log_alpha.copy_(a[0:1])
-    orc.opt_a.m["log_alpha"].copy_(a[1:2])
-    orc.opt_a.v["log_alpha"].copy_(a[2:3])
-    orc.opt_a.t = t
-    orc.n_steps = t
-    return orc
-
-
-def _oracle_tensors(meta, orc, out):
-    rec = {}
-    for grp, params, opt in (("policy", orc.P, orc.opt_p), ("qf1", orc.Q1, orc.opt_q1),
-                             ("qf2", orc.Q2, orc.opt_q2)):
-        for pn in params:
-            rec[f"grad/{grp}/{pn}"] = out["grads"][grp][pn].double().numpy().copy()
-            rec[f"post/{grp}/{pn}"] = params[pn].double().numpy().copy()
-            rec[f"adam/{grp}/{pn}/exp_avg"] = opt.m[pn].double().numpy().copy()
-            rec[f"adam/{grp}/{pn}/exp_avg_sq"] = opt.v[pn].double().numpy().copy()
-    for grp, params in (("target_qf1", orc.T1), ("target_qf2", orc.T2)):
-        for pn, t in params.items():
-            rec[f"post/{grp}/{pn}"] = t.double().numpy().copy()
-    if meta["auto_alpha"]:
-        rec["grad/log_alpha"] = out["grads"]["log_alpha"].double().numpy().copy()
-        rec["post/log_alpha"] = orc.log_alpha.double().numpy().copy()
-    return rec
-
-
-def _gpu_tensors(meta, tr):
-    rec = {}
-    for grp in ssl.GROUPS:
-        mod = getattr(tr, grp)
-        for what, arena in (("grad", tr.grads), ("post", tr.params)):
-            for pn, t in module_tensors(tr, mod, arena).items():
-                rec[f"{what}/{grp}/{pn}"] = t.cpu().numpy()
-        m, v = module_tensors(tr, mod, tr.adam_m), module_tensors(tr, mod, tr.adam_v)
-        for pn in m:
-            rec[f"adam/{grp}/{pn}/exp_avg"] = m[pn].cpu().numpy()
-            rec[f"adam/{grp}/{pn}/exp_avg_sq"] = v[pn].cpu().numpy()
-    for grp in ssl.TARGETS:
-        for pn, t in getattr(tr, grp).state_dict().items():
-            rec[f"post/{grp}/{pn}"] = t.cpu().numpy()
-    if meta["auto_alpha"]:
-        a = tr.alpha_state.cpu().numpy()
-        rec["grad/log_alpha"], rec["post/log_alpha"] = a[5:6].copy(), a[0:1].copy()
-    return rec
-
-
-def _step_against_oracle(tr, meta, batch, eps1, eps2, what):
-    """One step of the trainer and of the fp32 oracle from the trainer's own
-    pre-step state; {key: (error, gate)} for every tensor over its gate.  The
-    gate: 1e-5, or 3x the fp32 oracle's distance from the float64 oracle run
-    from the same state on the same inputs."""
-    o32, o64 = _oracle_from(tr, meta, torch.float32), _oracle_from(tr, meta, torch.float64)
-    tr.train_from_torch(batch, eps1=eps1, eps2=eps2)
-    torch.cuda.synchronize()
-    r32 = _oracle_tensors(meta, o32, o32.step(batch, eps1, eps2))
-    r64 = _oracle_tensors(meta, o64, o64.step(batch, eps1, eps2))
-    got = _gpu_tensors(meta, tr)
-    assert sorted(got) == sorted(r32)
-    errs = {k: parity.rel_err(got[k], r32[k]) for k in r32}
-    gates = {k: parity.gate(k, parity.rel_err(r32[k], r64[k])) for k in r32}
-    w = max(errs, key=lambda k: errs[k] / gates[k])
-    print(f"{what}: worst {w} {errs[w]:.2e} (gate {gates[w]:.2e}); widest gate {max(gates.values()):.2e}")
-    return {k: (errs[k], gates[k]) for k in errs if not errs[k] <= gates[k]}
+# (the helpers live in sac_shallow_lib: tests/test_gpu_shallow_wide.py runs them too)
+_oracle_from = ssl.oracle_from
+_step_against_oracle = ssl.step_against_oracle
 
 
 @pytest.mark.parametrize("name", ssl.STEP_FIXTURES)

@@ -341,3 +341,123 @@ def trainer_for(meta, params=None, **kw):
                                      **common)
     tr.q_producer_calls = qp.calls
     return tr
+
+
+# ------------------------------------------------- oracle from the GPU's state
+def _np_sd(mod):
+    return {k: v.detach().cpu().numpy().copy() for k, v in mod.state_dict().items()}
+
+
+def _load_adam(opt, tr, mod):
+    from gpu_helpers import module_tensors
+    m, v = module_tensors(tr, mod, tr.adam_m), module_tensors(tr, mod, tr.adam_v)
+    for k in opt.m:
+        opt.m[k].copy_(m[k].detach().cpu())
+        opt.v[k].copy_(v[k].detach().cpu())
+    opt.t = tr._n_train_steps_total
+
+
+def oracle_from_gpu(tr, meta, g=None, dtype=torch.float32):
+    """The oracle (fp32 unless ``dtype`` says otherwise) holding the GPU
+    trainer's current state (teacher forcing)."""
+    torch.cuda.synchronize()
+    params = dict(policy=_np_sd(tr.policy), target_policy=_np_sd(tr.target_policy),
+                  qfs=[_np_sd(q) for q in tr.qfs], tfs=[_np_sd(t) for t in tr.tfs])
+    orc = make_oracle(meta, dtype=dtype, g=g, params=params)
+    _load_adam(orc.opt_p, tr, tr.policy)
+    _load_adam(orc.opt_tp, tr, tr.target_policy)
+    for opt, q in zip(orc.opts, tr.qfs):
+        _load_adam(opt, tr, q)
+    orc.n_steps = tr._n_train_steps_total
+    return orc
+
+
+def _groups(tr, orc, meta):
+    K = n_critics(meta)
+    gs = [("policy", tr.policy, orc.P, orc.opt_p, meta["lr"]),
+          ("target_policy", tr.target_policy, orc.TP, orc.opt_tp, meta["lr"])]
+    return gs + [(f"qf{k}", tr.qfs[k], orc.Qs[k], orc.opts[k], critic_lr(meta, k))
+                 for k in range(K)]
+
+
+def step_tensors(orc, out, meta, tr=None):
+    """{key: array} of a step just taken, keyed as step_errors_against_oracle
+    keys its errors: the oracle's (``tr`` None) or the GPU trainer's.  The K
+    critics' last biases are gathered into the [K] vector 'qf*'."""
+    from gpu_helpers import module_tensors
+    rec, stacked = {}, {}
+    K = n_critics(meta)
+    groups = [("policy", orc.P, orc.opt_p), ("target_policy", orc.TP, orc.opt_tp)]
+    groups += [(f"qf{k}", orc.Qs[k], orc.opts[k]) for k in range(K)]
+    for grp, want, opt in groups:
+        if tr is not None:
+            mod = tr.qfs[int(grp[2:])] if grp.startswith("qf") else getattr(tr, grp)
+            gv = module_tensors(tr, mod, tr.grads)
+            mv, vv = module_tensors(tr, mod, tr.adam_m), module_tensors(tr, mod, tr.adam_v)
+            sd = mod.state_dict()
+            get = lambda d, pn: d[pn].detach().cpu().double().numpy()
+            vals = lambda pn: (get(gv, pn), get(sd, pn), get(mv, pn), get(vv, pn))
+        else:
+            get = lambda d, pn: d[pn].double().numpy().copy()
+            vals = lambda pn: (get(out["grads"][grp], pn), get(want, pn), get(opt.m, pn), get(opt.v, pn))
+        for pn in want:
+            for what, v in zip(("grad", "post", "adam_m", "adam_v"), vals(pn)):
+                if grp.startswith("qf") and pn == "last_fc.bias":
+                    stacked.setdefault(what, []).append(float(v.reshape(-1)[0]))
+                else:
+                    rec[f"{what}/{grp}/{pn}"] = v
+    for what, v in stacked.items():
+        rec[f"{what}/qf*/last_fc.bias"] = np.array(v)
+    for k in range(K):
+        src = tr.tfs[k].state_dict() if tr is not None else orc.Ts[k]
+        for pn, t in src.items():
+            rec[f"post/tf{k}/{pn}"] = t.detach().cpu().double().numpy()
+    return rec
+
+
+def step_errors_against_oracle(tr, orc, out, meta):
+    """{key: error} of the GPU step just taken against the oracle's step from
+    the same pre-step state: every gradient, post-step parameter and Adam
+    moment of every network, and every target critic, norm-relative per tensor.
+
+    A critic's last_fc.bias is ONE number, and its gradient sum_r dq[r] a sum of
+    B terms of both signs: two correct fp32 sums differ by ~B eps sum|dq[r]|,
+    which relative to the sum itself is unbounded (cancellation) -- a [K]
+    vector's norm averages that out, a scalar's does not.  The K critics'
+    biases (gradient, Adam moments, post-step value) are therefore compared as
+    the [K] vector they form in the stacked block (key 'qf*'), which is also
+    what the shared-layer step's last_fc.bias is."""
+    from gpu_helpers import module_tensors
+    torch.cuda.synchronize()
+    errs = {}
+    stacked = {}
+    for grp, mod, want, opt, lr in _groups(tr, orc, meta):
+        gv = module_tensors(tr, mod, tr.grads)
+        mv, vv = module_tensors(tr, mod, tr.adam_m), module_tensors(tr, mod, tr.adam_v)
+        sd = mod.state_dict()
+        for pn in want:
+            gref = out["grads"][grp][pn].numpy()
+            if grp.startswith("qf") and pn == "last_fc.bias":
+                for what, got, ref in (("grad", gv[pn], gref), ("post", sd[pn], want[pn].numpy()),
+                                       ("adam_m", mv[pn], opt.m[pn].numpy()),
+                                       ("adam_v", vv[pn], opt.v[pn].numpy())):
+                    a, b = stacked.setdefault(what, ([], []))
+                    a.append(float(got.cpu().reshape(-1)[0]))
+                    b.append(float(np.asarray(ref).reshape(-1)[0]))
+                continue
+            errs[f"grad/{grp}/{pn}"] = parity.rel_err(gv[pn].cpu().numpy(), gref)
+            errs[f"post/{grp}/{pn}"], _ = parity.compare_post(
+                {"p": want[pn].numpy(), "g": gref}, "p", "g", sd[pn].cpu().numpy(), lr)
+            errs[f"adam_m/{grp}/{pn}"] = parity.rel_err(mv[pn].cpu().numpy(), opt.m[pn].numpy())
+            errs[f"adam_v/{grp}/{pn}"] = parity.rel_err(vv[pn].cpu().numpy(), opt.v[pn].numpy())
+    lr = meta["lr"]
+    for what, (got, ref) in stacked.items():
+        if what == "post":   # (outside Adam's sign band of the gradient vector, as compare_post)
+            errs["post/qf*/last_fc.bias"], _ = parity.compare_post(
+                {"p": np.array(ref), "g": np.array(stacked["grad"][1])}, "p", "g", np.array(got), lr)
+        else:
+            errs[f"{what}/qf*/last_fc.bias"] = parity.rel_err(got, ref)
+    for k, tf in enumerate(tr.tfs):
+        for pn, t in tf.state_dict().items():
+            errs[f"post/tf{k}/{pn}"] = parity.rel_err(t.cpu().numpy(), orc.Ts[k][pn].numpy())
+    return errs
