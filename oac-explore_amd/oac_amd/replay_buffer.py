@@ -342,20 +342,37 @@ class DeviceIndexStream:
     """A ring of pre-drawn batch indices for ``SACTrainer.train_from_ring``:
     2*chunk step slots, refilled one chunk ahead by the device MT19937 kernel
     (sequential in the stream, so the index sequence equals
-    ``np.random.seed(seed); randint(0, size, B)`` called once per step)."""
+    ``np.random.seed(seed); randint(0, size, B)`` called once per step).
 
-    def __init__(self, buffer, batch_size, chunk=64, seed=1):
+    A ring step reads slot ``batch_counter % slots`` (gather_kernel), so stream
+    step k lives in slot ``(start + k) % slots``: ``start`` is the trainer's
+    batch counter (``step_state[1]``) at the stream's first step -- 0 for a
+    fresh trainer, the number of gradient steps already taken otherwise.  With
+    another ``start`` than the trainer's counter the steps read slots in a
+    rotated order (the first draws skipped, or a stale half first)."""
+
+    def __init__(self, buffer, batch_size, chunk=64, seed=1, start=0):
         self.buf, self.B, self.chunk = buffer, int(batch_size), int(chunk)
         self.slots = 2 * self.chunk
+        self.start = int(start)
+        if self.start < 0:
+            raise ValueError("start is a batch counter: it must be >= 0")
         self.ring = torch.empty(self.slots * self.B, dtype=torch.int32, device=buffer.device)
         buffer.seed_device_stream(seed)
         self.t = 0
         self._fill(0)
-        self._fill(1)
+        self._fill(self.chunk)
 
-    def _fill(self, half):
-        view = self.ring[half * self.chunk * self.B:(half + 1) * self.chunk * self.B]
-        self.buf.sample_indices_device(self.chunk * self.B, out=view)
+    def _fill(self, k0):
+        """Stream steps k0 .. k0 + chunk - 1 into their slots (two pieces when
+        they wrap the ring's end; the stream carries from call to call)."""
+        s0 = (self.start + k0) % self.slots
+        first = min(self.chunk, self.slots - s0)
+        self.buf.sample_indices_device(first * self.B,
+                                       out=self.ring[s0 * self.B:(s0 + first) * self.B])
+        if first < self.chunk:
+            self.buf.sample_indices_device((self.chunk - first) * self.B,
+                                           out=self.ring[:(self.chunk - first) * self.B])
 
     def before_step(self, n_steps=1):
         """Call before each ring step (or block of n_steps consecutive steps,
@@ -363,5 +380,5 @@ class DeviceIndexStream:
         if self.chunk % n_steps or self.t % n_steps:
             raise ValueError("n_steps must divide the ring chunk and the step count")
         if self.t > 0 and self.t % self.chunk == 0:
-            self._fill(((self.t // self.chunk) + 1) % 2)
+            self._fill(self.t + self.chunk)   # over the slots of steps t - chunk .. t - 1
         self.t += n_steps
