@@ -416,6 +416,48 @@ int64_t oac_replay_priority_scratch_doubles(int64_t size);
 int oac_replay_priority_sample(const int32_t* counts, int64_t size, const double* u, int B,
                                double* scratch, int32_t* idx_out, void* stream);
 
+/* ReplayBufferNoResampling (replay_buffer_no_resampling.py:8-173): the use-once
+ * buffer.  Device state, all int32 and owned by the caller: two list buffers
+ * valid[capacity] (the ordered live slots, _valid_indeces; a take reads one and
+ * writes the other) and queue[capacity] (the ring of freed slots,
+ * indices_to_replace).  The caller keeps every length and counter; nothing is
+ * read back.  capacity < 2^31.
+ *
+ * take (random_batch / add_indices_to_replace): B distinct positions of
+ * valid_in[0:len) -- device int32 [B], or NULL: drawn on the device as
+ * oac_replay_nr_sample_positions(len, B, seed, draw_counter) draws them --
+ *   idx_out[b] = valid_in[positions[b]]                     (draw order)
+ *   queue[(top_indexes + b) % capacity] = idx_out[b]
+ *   valid_out[0 : len - B) = valid_in without those positions, order kept
+ * positions_out (may be NULL) receives the positions used; scratch: int32 [B];
+ * valid_out must not alias valid_in.  1 <= B <= min(len, 4096).  At most two
+ * launches. */
+int oac_replay_nr_take(const int32_t* valid_in, int64_t len, const int32_t* positions, int B,
+                       int32_t* queue, int64_t capacity, int64_t top_indexes, int32_t* idx_out,
+                       int32_t* positions_out, int32_t* valid_out, int32_t* scratch, uint64_t seed,
+                       uint64_t draw_counter, void* stream);
+/* B distinct positions of [0, n), Floyd's subset sampling on Philox4x32-10:
+ * for t = 0 .. B-1, j = n - B + t: counter words {t, 4, draw_counter lo, hi},
+ * key = seed, w = (word0 << 32) | word1, r = mulhi64(w, j + 1), pick_t = r
+ * unless r is among pick_0 .. pick_{t-1}, then j.  1 <= B <= min(n, 4096),
+ * n < 2^31.  One launch. */
+int oac_replay_nr_sample_positions(int64_t n, int B, uint64_t seed, uint64_t draw_counter,
+                                   int32_t* positions_out, void* stream);
+/* insert (add_sample, :98-122) of n rows: oac_replay_insert's packing at
+ *   slot(s) = s < queue_entries ? queue[(bottom_indexes + s) % capacity]
+ *                               : (top + s - queue_entries) % capacity
+ * and valid[len + s] = slot(s); len + n <= capacity.  One launch. */
+int oac_replay_nr_insert(float* storage, int64_t row_stride, int64_t capacity, int64_t top,
+                         const int32_t* queue, int64_t bottom_indexes, int64_t queue_entries,
+                         int32_t* valid, int64_t len, int n, const double* obs, const double* act,
+                         const double* rew, const double* next_obs, const uint8_t* term, int obs_dim,
+                         int act_dim, int off_obs, int off_act, int off_rew, int off_term,
+                         int off_next_obs, void* stream);
+/* list elements per workgroup of the take's compaction launch, and the number
+ * of kernel launches the three entry points above have issued in this process */
+int64_t oac_replay_nr_chunk(void);
+int64_t oac_replay_nr_launch_count(void);
+
 /* ------------------------------------------------------------------ Adam */
 /* advance 0: Adam step t = n_steps+1, snapshot t (step_state), Polyak when
  * n_steps % period == 0; advance 1: t from the snapshot, then n_steps += 1. */

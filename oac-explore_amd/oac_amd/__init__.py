@@ -11,6 +11,7 @@ Drop-in replacements for the reference's hot-path interfaces:
   DDPGTrainer                        trainer/ddpg_trainer.py (--alg ddpg)
   get_optimistic_exploration_action  optimistic_exploration.py
   ReplayBuffer, ReplayBufferCount    replay_buffer.py
+  ReplayBufferNoResampling           replay_buffer_no_resampling.py (--no_resampling)
   vec_rollout                        path_collector.py rollout over N envs, one call per step
 backed by liboac_amd.so (hand-written HIP for gfx950 behind a C ABI).
 """
@@ -20,7 +21,8 @@ from .particle_trainer import ParticleTrainer  # noqa: F401
 from .particle_trainer_oac import ParticleTrainer as ParticleTrainerOAC  # noqa: F401
 from .gaussian_trainer import GaussianTrainer  # noqa: F401
 from .ddpg_trainer import DDPGTrainer  # noqa: F401
-from .replay_buffer import ReplayBuffer, ReplayBufferCount, DeviceBatch, DeviceIndexStream  # noqa: F401
+from .replay_buffer import (ReplayBuffer, ReplayBufferCount, ReplayBufferNoResampling,  # noqa: F401
+                            DeviceBatch, DeviceIndexStream)
 from .optimistic_exploration import (get_optimistic_exploration_action,  # noqa: F401
                                      get_optimistic_exploration_actions)
 from .producers import get_policy_producer, get_q_producer  # noqa: F401

@@ -218,6 +218,21 @@ _SIGS = {
     "oac_replay_priority_sample": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
                                                   ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
                                                   ctypes.c_void_p]),
+    "oac_replay_nr_take": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
+                                          ctypes.c_int, ctypes.c_void_p, ctypes.c_int64,
+                                          ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
+                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
+                                          ctypes.c_uint64, ctypes.c_void_p]),
+    "oac_replay_nr_sample_positions": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, ctypes.c_uint64,
+                                                      ctypes.c_uint64, ctypes.c_void_p,
+                                                      ctypes.c_void_p]),
+    "oac_replay_nr_insert": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
+                                            ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64,
+                                            ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64,
+                                            ctypes.c_int] + [ctypes.c_void_p] * 5 +
+                             [ctypes.c_int] * 7 + [ctypes.c_void_p]),
+    "oac_replay_nr_chunk": (ctypes.c_int64, []),
+    "oac_replay_nr_launch_count": (ctypes.c_int64, []),
     "oac_adam_polyak": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                        ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
                                        ctypes.c_float, ctypes.c_int, ctypes.c_double,

@@ -382,3 +382,235 @@ class DeviceIndexStream:
         if self.t > 0 and self.t % self.chunk == 0:
             self._fill(self.t + self.chunk)   # over the slots of steps t - chunk .. t - 1
         self.t += n_steps
+
+
+class ReplayBufferNoResampling(ReplayBuffer):
+    """Drop-in ``ReplayBufferNoResampling`` (replay_buffer_no_resampling.py:8-173),
+    the buffer of ``--no_resampling``: every transition is drawn exactly once and
+    its slot is then handed to the next insert.
+
+    The rows, the ordered list of live slots (``_valid_indeces``) and the ring of
+    freed slots (``indices_to_replace``) live on the device; the host keeps the
+    reference's five counters (``_top``, ``_bottom_indexes``, ``_top_indexes``,
+    ``_size`` and the list's length) with the reference's own arithmetic, the
+    ring's aliasing included (N freed slots make the ring read as empty).
+
+    ``random_batch(B)`` takes B distinct POSITIONS of the list:
+    ``index_source='numpy'`` draws ``np.random.choice(len, size=B,
+    replace=False)`` on the global stream -- the reference's
+    ``np.random.choice(self._valid_indeces, ...)`` picks the list's entries at
+    exactly these positions and leaves the stream in the same state;
+    ``'device'`` draws them with Floyd's sampling on Philox (no host work
+    proportional to the list, no copy back, no synchronisation).  The take
+    kernels gather the slots in draw order, push them on the ring and compact
+    the list (oac_replay_nr_take, two launches).
+
+    Deviations from the reference:
+
+    1. An insert of m rows with live + m > capacity raises ``RuntimeError``
+       before changing anything (the reference wraps ``_top`` onto a live slot,
+       overwrites it and lists it twice).  The ``--no_resampling`` schedule never
+       gets there.
+    2. ``restore_from_snapshot`` restores every key of ``get_snapshot`` (the
+       reference asserts on a misspelt attribute and cannot run).
+    3. ``random_batch(B)`` with B > live raises numpy's ``ValueError`` with
+       numpy's words from either index source; nothing changes.
+
+    A take handles at most 4096 positions (they are sorted in LDS).
+    ``get_dataset`` raises: the reference class has none, and the live rows are
+    scattered over the store."""
+
+    MAX_BATCH = 4096
+    SNAPSHOT_KEYS = ("_observations", "_next_obs", "_actions", "_rewards", "_terminals", "_top",
+                     "_indices_to_replace", "_bottom_indexes", "_top_indexes", "_valid_indeces",
+                     "_size")
+
+    def __init__(self, max_replay_buffer_size, ob_space, action_space, device=None,
+                 index_source="numpy", seed=None):
+        if index_source not in ("numpy", "device"):
+            raise ValueError(f"ReplayBufferNoResampling: index_source {index_source!r}")
+        super().__init__(max_replay_buffer_size, ob_space, action_space, device=device,
+                         index_source="numpy")
+        N = self._max_replay_buffer_size
+        if N >= 1 << 31:
+            raise ValueError(f"ReplayBufferNoResampling: capacity {N} >= 2^31")
+        self.index_source = index_source
+        self._valid = [torch.zeros(N, dtype=torch.int32, device=self.device) for _ in range(2)]
+        self._cur = 0        # which list buffer is current
+        self._live = 0       # len(_valid_indeces)
+        self._queue = torch.zeros(N, dtype=torch.int32, device=self.device)
+        self._bottom_indexes = 0
+        self._top_indexes = 0
+        self._shift = torch.empty(self.MAX_BATCH, dtype=torch.int32, device=self.device)
+        self._seed, self._draws = 0, 0
+        self.seed_device_stream(0 if seed is None else seed)
+
+    # ------------------------------------------------------------ insert
+    def _insert(self, obs, act, rew, nobs, term):
+        """add_sample (:98-122) for m rows in one launch: the first q rows go to
+        the ring's slots, the rest to _top onward; every slot is appended to
+        the live list."""
+        m = len(obs)
+        if m == 0:
+            return
+        N = self._max_replay_buffer_size
+        if self._live + m > N:
+            raise RuntimeError(
+                f"ReplayBufferNoResampling: inserting {m} rows over {self._live} live rows "
+                f"exceeds the capacity {N} (a live row would be written over)")
+        q = (self._top_indexes - self._bottom_indexes) % N
+
+        def dev(x, dt, shape):
+            return torch.from_numpy(np.ascontiguousarray(np.asarray(x, dt).reshape(shape))).to(
+                self.device)
+        o = dev(obs, np.float64, (m, self.ob_dim))
+        a = dev(act, np.float64, (m, self.ac_dim))
+        r = dev(rew, np.float64, (m,))
+        no = dev(nobs, np.float64, (m, self.ob_dim))
+        t = dev(np.asarray(term).reshape(m).astype(np.uint8), np.uint8, (m,))
+        lay = self.rows
+        check(_lib.lib().oac_replay_nr_insert(
+            ptr(self._storage), lay["row_stride"], N, self._top, ptr(self._queue),
+            self._bottom_indexes, q, ptr(self._valid[self._cur]), self._live, m, ptr(o), ptr(a),
+            ptr(r), ptr(no), ptr(t), self.ob_dim, self.ac_dim, lay["off_obs"], lay["off_act"],
+            lay["off_rew"], lay["off_term"], lay["off_next_obs"], stream_ptr()))
+        k = min(m, q)                                   # _advance, :116-122
+        self._bottom_indexes = (self._bottom_indexes + k) % N
+        self._top = (self._top + m - k) % N
+        self._size = min(self._size + m, N)
+        self._live += m
+
+    def load_transitions(self, rows_fp32):
+        """Bulk fill of an EMPTY buffer with pre-built rows [n, row_stride]: slots
+        0 .. n-1 in order, as n add_sample calls would leave them."""
+        if self._live or self._top or self._top_indexes != self._bottom_indexes:
+            raise RuntimeError("ReplayBufferNoResampling.load_transitions: the buffer is not empty")
+        n = rows_fp32.shape[0]
+        assert rows_fp32.shape[1] == self.rows["row_stride"] and n <= self._max_replay_buffer_size
+        self._storage[:n].copy_(rows_fp32)
+        self._valid[self._cur][:n].copy_(torch.arange(n, dtype=torch.int32, device=self.device))
+        self._top = n % self._max_replay_buffer_size
+        self._size = self._live = n
+
+    # ------------------------------------------------------------ sample
+    def seed_device_stream(self, seed):
+        """Key of the device position draw; restarts its draw counter."""
+        self._seed, self._draws = int(seed) & (2 ** 64 - 1), 0
+
+    def sample_positions_device(self, n, batch_size, draw_counter=None):
+        """The device draw alone: B distinct positions of [0, n) for draw
+        ``draw_counter`` (default: the buffer's counter, which is NOT advanced)."""
+        B = int(batch_size)
+        d = self._draws if draw_counter is None else int(draw_counter)
+        out = torch.empty(max(B, 1), dtype=torch.int32, device=self.device)
+        check(_lib.lib().oac_replay_nr_sample_positions(
+            int(n), B, ctypes.c_uint64(self._seed), ctypes.c_uint64(d), ptr(out), stream_ptr()))
+        return out[:B]
+
+    def _check_batch(self, B):
+        if B > self._live:   # numpy's own refusal, np.random.choice(live, B, replace=False)
+            raise ValueError("Cannot take a larger sample than population when 'replace=False'")
+        if B < 1:
+            raise ValueError("ReplayBufferNoResampling: batch_size must be >= 1")
+        if B > self.MAX_BATCH:
+            raise ValueError(f"ReplayBufferNoResampling: batch_size {B} > {self.MAX_BATCH}")
+
+    def _take_device(self, positions, B):
+        """One take (positions: device int32 [B], or None = device draw):
+        (slots, positions used) as device tensors; the counters advance as
+        add_indices_to_replace (:91-96) moves them."""
+        N = self._max_replay_buffer_size
+        idx = torch.empty(B, dtype=torch.int32, device=self.device)
+        pos = torch.empty(B, dtype=torch.int32, device=self.device)
+        src, dst = self._valid[self._cur], self._valid[1 - self._cur]
+        check(_lib.lib().oac_replay_nr_take(
+            ptr(src), self._live, ptr(positions), B, ptr(self._queue), N, self._top_indexes,
+            ptr(idx), ptr(pos), ptr(dst), ptr(self._shift), ctypes.c_uint64(self._seed),
+            ctypes.c_uint64(self._draws), stream_ptr()))
+        self._cur = 1 - self._cur
+        self._live -= B
+        self._top_indexes = (self._top_indexes + B) % N
+        self._size -= B
+        return idx, pos
+
+    def _take(self, positions):
+        """Take the list's entries at the given distinct host positions (any
+        order): the drawn slots in that order, a device int32 tensor."""
+        p = np.asarray(positions).reshape(-1)
+        B = len(p)
+        self._check_batch(B)
+        p = p.astype(np.int64)
+        if p.min() < 0 or p.max() >= self._live or len(np.unique(p)) != B:
+            raise ValueError("ReplayBufferNoResampling._take: positions must be distinct and in "
+                             f"[0, {self._live})")
+        return self._take_device(torch.from_numpy(p.astype(np.int32)).to(self.device), B)[0]
+
+    def random_batch(self, batch_size):
+        """replay_buffer_no_resampling.py:124-141."""
+        B = int(batch_size)
+        self._check_batch(B)   # before the stream moves
+        if self.index_source == "device":
+            idx, _ = self._take_device(None, B)
+            self._draws += 1
+        else:
+            idx = self._take(np.random.choice(self._live, size=B, replace=False))
+        return DeviceBatch(self, idx)
+
+    def add_indices_to_replace(self, indices):
+        """:91-96 for slot VALUES: each is pushed on the ring and its first
+        occurrence leaves the list.  Not on random_batch's path: it downloads
+        the list to find the positions (a synchronisation)."""
+        indices = [int(i) for i in indices]
+        if not indices:
+            return
+        lst = self._valid[self._cur][:self._live].cpu().numpy()
+        order = np.argsort(lst, kind="stable")
+        at = np.searchsorted(lst[order], indices)
+        if (at >= len(lst)).any() or (lst[order][np.minimum(at, len(lst) - 1)] != indices).any() \
+                or len(set(indices)) != len(indices):
+            raise ValueError("list.remove(x): x not in list")
+        self._take(order[at])
+
+    # ------------------------------------------------------------ misc
+    def get_dataset(self):
+        raise NotImplementedError(
+            "ReplayBufferNoResampling has no get_dataset (the reference class has none; the live "
+            "rows are scattered over the store)")
+
+    def sample_indices_device(self, count, out=None):
+        raise NotImplementedError(
+            "ReplayBufferNoResampling draws without replacement: use random_batch")
+
+    def valid_indices(self):
+        """The live list (_valid_indeces) as a device int32 tensor, in order."""
+        return self._valid[self._cur][:self._live]
+
+    def get_snapshot(self):
+        """The reference's eleven keys and dtypes (:154-167)."""
+        ss = super().get_snapshot()
+        ss.update(
+            _indices_to_replace=self._queue.cpu().numpy().astype(np.uint64),
+            _bottom_indexes=self._bottom_indexes, _top_indexes=self._top_indexes,
+            _valid_indeces=[int(i) for i in self.valid_indices().cpu().numpy()])
+        return ss
+
+    def restore_from_snapshot(self, ss):
+        """Every key of get_snapshot (the reference's evident intent, :169-173)."""
+        for key in ss.keys():
+            assert key in self.SNAPSHOT_KEYS, key
+        N = self._max_replay_buffer_size
+        lst = np.asarray(ss["_valid_indeces"], np.int64).reshape(-1)
+        q = np.asarray(ss["_indices_to_replace"]).reshape(-1)
+        if len(lst) > N or len(q) != N:
+            raise ValueError("ReplayBufferNoResampling.restore_from_snapshot: wrong capacity")
+        if (len(lst) and (lst.min() < 0 or lst.max() >= N)) or q.max() >= N:
+            raise ValueError("ReplayBufferNoResampling.restore_from_snapshot: a slot >= capacity")
+        rows = self._rows_from(ss["_observations"], ss["_actions"], ss["_rewards"],
+                               ss["_next_obs"], ss["_terminals"])
+        self._storage[:len(rows)].copy_(torch.from_numpy(rows))
+        self._queue.copy_(torch.from_numpy(q.astype(np.int64).astype(np.int32)))
+        self._valid[self._cur][:len(lst)].copy_(torch.from_numpy(lst.astype(np.int32)))
+        self._live = len(lst)
+        self._top, self._size = int(ss["_top"]), int(ss["_size"])
+        self._bottom_indexes = int(ss["_bottom_indexes"])
+        self._top_indexes = int(ss["_top_indexes"])
