@@ -358,7 +358,7 @@ int oac_rccl_allreduce(void* rccl, float* buf, int64_t n, void* stream);
 #define OAC_TRACE_SPLIT_PHASE1  32   /* phase 1 issued as 4 + 5 (the overlapped alpha exchange) */
 #define OAC_TRACE_FUSED         64   /* the single-process fused-Adam step */
 #define OAC_TRACE_EXCHANGE      128  /* data-parallel exchanges issued through the hook */
-#define OAC_TRACE_LA_ADAM       256  /* large batch: policy layer-0 Adam by last arrival (no launch) */
+/* bit 256: unused (was the last-arrival Adam's, removed with it) */
 #define OAC_TRACE_HEAD_DH2      512  /* the head's dX in the dL/da launch, head dW with policy layer 1 */
 int oac_sac_trace(oac_sac* h, int reset);
 
@@ -590,9 +590,10 @@ int oac_abi_version(void);
    and the alternative-kernel parity tests (no reference counterpart).  The
    library reads no environment variable: a process sets a choice with
    oac_tuning_set (0 = the default) before it creates the plans that use it.
-   Returns 1 for an unknown key. */
+   Returns 1 for an unknown key, and for a retired key with a non-zero value
+   (the choice no longer exists; 0 is accepted). */
 enum oac_tuning_key {
-  OAC_TUNE_BWDP_CFG = 0,     /* large-batch backward tile config: 9-15, 17 (default: 12, 64x64 2-stage) */
+  OAC_TUNE_RETIRED_0 = 0,    /* was the backward tile configuration choice; the next ABI-breaking change drops it */
   OAC_TUNE_FWD_TILE_M,       /* large-batch forward tile rows: 64 / 128 (default: per launch) */
   OAC_TUNE_FWD_TILE_N,       /* large-batch forward tile columns: 64 / 128 */
   OAC_TUNE_FWD_NB,           /* large-batch forward LDS ring depth: 2 / 3 */
@@ -611,8 +612,7 @@ enum oac_tuning_key {
   OAC_TUNE_RING_PREFETCH,    /* 1: on that gather-launch path, the next step's critic-side
                                 forward inside the policy backward (instead of the deferred
                                 layer-0 Adam) */
-  OAC_TUNE_LA_ADAM,          /* 1: the large-batch SAC step's policy layer-0 Adam by the last
-                                arrival of each dW tile (no Adam launch) */
+  OAC_TUNE_RETIRED_15,       /* was the last-arrival Adam switch; the next ABI-breaking change drops it */
   OAC_TUNE_HEAD_DH2,         /* -1: the small-batch SAC step's policy-head dX in the head-dW
                                 launch instead of in the dL/da launch's epilogue (the default,
                                 which merges the head dW into the policy layer-1 backward

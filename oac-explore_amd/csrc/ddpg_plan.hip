@@ -68,7 +68,7 @@ enum DWs {
   D_QSHADOW,   // fused small-batch step: the critic's post-step layer 1 + last layer
   D_COUNT
 };
-static_assert(D_COUNT <= WS_TICKETS, "workspace ids");
+static_assert(D_COUNT <= WS_GSLAB_Q, "workspace ids");
 
 int ddpg_shadow_ws() { return D_QSHADOW; }
 

@@ -1145,7 +1145,7 @@ __global__ void __launch_bounds__(1024) oac_expl_twin_kernel(ExplFusedArgs a, in
 long expl_split_scratch_floats(int H) { return expl_split_scratch(H); }
 
 // threads per workgroup: 1024.  Humanoid, one observation, host wall per call
-// (round 2, tools/gpu_expl_ab.sh): 256 / 512 / 1024 threads 54.6 / 46.5 / 45.2
+// (round 2, same-box A/B): 256 / 512 / 1024 threads 54.6 / 46.5 / 45.2
 // us at 16 workgroups per row; 1024 threads 49.4 / 45.2 / 44.4 us at 8 / 16 /
 // 32 workgroups per row
 int expl_split_threads() { return 1024; }

@@ -352,18 +352,17 @@ hipError_t gemm_fwd_launch(const GemmBatch& b, int cfg, hipStream_t s, BatchCach
 int gemm_fwd_tile_m(int cfg);
 int gemm_fwd_tile_n(int cfg);
 
-hipError_t gemm_bwdp_launch(const GemmBatch& b, int cfg, hipStream_t s, BatchCache* bc = nullptr,
-                            int pos = -1);
-int gemm_bwdp_tile_m(int cfg);
-int gemm_bwdp_tile_n(int cfg);
+hipError_t gemm_bwdp_launch(const GemmBatch& b, hipStream_t s, BatchCache* bc = nullptr, int pos = -1);
+int gemm_bwdp_tile_m();
+int gemm_bwdp_tile_n();
 
 int gemm_tile_m(int cfg) {
-  if (cfg >= 9) return gemm_bwdp_tile_m(cfg);
+  if (cfg == kCfgBwdp) return gemm_bwdp_tile_m();
   if (cfg >= 6) return gemm_fwd_tile_m(cfg);
   return cfg == 0 ? 32 : 64;
 }
 int gemm_tile_n(int cfg) {
-  if (cfg >= 9) return gemm_bwdp_tile_n(cfg);
+  if (cfg == kCfgBwdp) return gemm_bwdp_tile_n();
   if (cfg >= 6) return gemm_fwd_tile_n(cfg);
   return cfg == 0 ? 32 : 64;
 }
@@ -380,8 +379,8 @@ void gemm_batch_finalize(GemmBatch& b, int cfg) {
   for (int i = 0; i < b.ntasks; ++i) {
     GemmTask& t = b.t[i];
     const int tm = (t.M + bm - 1) / bm;
-    // gemm_bwdp.hip (cfg 9-11): a dW's ones column is not a column tile
-    const int nx = (cfg >= 9 && t.epi == EPI_GRAD && t.b_ones) ? t.N - 1 : t.N;
+    // gemm_bwdp.hip: a dW's ones column is not a column tile
+    const int nx = (cfg == kCfgBwdp && t.epi == EPI_GRAD && t.b_ones) ? t.N - 1 : t.N;
     const int tn = (nx + bn - 1) / bn;
     t.tile_begin = tiles;
     t.tiles_n = tn;
@@ -393,9 +392,7 @@ void gemm_batch_finalize(GemmBatch& b, int cfg) {
 
 hipError_t gemm_batch_launch(const GemmBatch& b, int cfg, hipStream_t s, BatchCache* bc, int pos) {
   if (b.total_tiles <= 0) return hipSuccess;
-  if (b.side_adam > 0 && (cfg < 9 || cfg > 17)) return hipErrorInvalidValue;   // side Adam: gemm_bwdp only
-  if (b.la_adam && (cfg != 12 || b.total_tiles > kLaTickets))   // last-arrival Adam: gemm_bwdp cfg 12
-    return hipErrorInvalidValue;
+  if (b.side_adam > 0 && cfg != kCfgBwdp) return hipErrorInvalidValue;   // side Adam: gemm_bwdp only
   // rows read through the direct gather's index slot (a_rows) and the side
   // workgroups that copy the batch / draw eps (rg): only the small kernel and
   // gemm_fwd implement them -- any other kernel would read replay rows 0..M-1
@@ -414,7 +411,7 @@ hipError_t gemm_batch_launch(const GemmBatch& b, int cfg, hipStream_t s, BatchCa
     // the width-1 head dot: small kernel or gemm_fwd (6-8)
     if (b.t[i].epi == EPI_BIAS_RELU_DOT && (cfg < 6 || cfg > 8)) return hipErrorInvalidValue;
   }
-  if (cfg >= 9) return gemm_bwdp_launch(b, cfg, s, bc, pos);
+  if (cfg == kCfgBwdp) return gemm_bwdp_launch(b, s, bc, pos);
   if (cfg >= 6) return gemm_fwd_launch(b, cfg, s, bc, pos);
   if (cfg != 1) return hipErrorInvalidValue;
   OAC_LAUNCH(gemm_grouped_kernel<CfgLarge>, dim3(b.total_tiles), dim3(256), 0, s, b);

@@ -735,7 +735,8 @@ void gemm_small_finalize(GemmBatch& b) {
 // (bc / pos: the launch records in device memory, kernels.h BatchCache -- not
 // taken here: at B=256 the small kernel's launches measured the same either way,
 // some launches 0.3-0.6 us faster and others as much slower, where the
-// pipelined large-batch kernels gained, tools/gpu_r5_t14.sh)
+// pipelined large-batch kernels gained: docs/design_log_r1_r5.md, "launch
+// records in device memory")
 hipError_t gemm_small_launch(const GemmBatch& b0, hipStream_t s, BatchCache* bc = nullptr, int pos = -1) {
   (void)bc; (void)pos;
   if (b0.total_tiles <= 0) return hipSuccess;

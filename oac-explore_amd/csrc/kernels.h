@@ -538,7 +538,10 @@ inline BatchCache::~BatchCache() {
 }
 
 
-// launchers (defined in the .hip files)
+// launchers (defined in the .hip files).  Launch-level tile configurations:
+// 0 = gemm_small.hip, 1 = the LDS-tiled kernel of gemm.hip, 6-8 = gemm_fwd.hip,
+// kCfgBwdp = gemm_bwdp.hip's one configuration (64x64 tiles, 2-stage ring)
+constexpr int kCfgBwdp = 12;
 void gemm_batch_finalize(GemmBatch& b, int cfg);
 hipError_t gemm_batch_launch(const GemmBatch& b, int cfg, hipStream_t s, BatchCache* bc = nullptr,
                              int pos = -1);

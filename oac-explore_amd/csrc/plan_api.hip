@@ -186,6 +186,12 @@ int oac_abi_version(void) { return OAC_ABI_VERSION; }
 
 int oac_tuning_set(int key, int value) {
   if (key < 0 || key >= OAC_TUNE_COUNT) { set_error("unknown tuning key %d", key); return 1; }
+  if (value != 0 && (key == OAC_TUNE_RETIRED_0 || key == OAC_TUNE_RETIRED_15)) {
+    set_error("tuning key %d (%s) was removed: the backward GEMM has one configuration", key,
+              key == OAC_TUNE_RETIRED_0 ? "OAC_TUNE_RETIRED_0, the backward tile configuration"
+                                        : "OAC_TUNE_RETIRED_15, the last-arrival Adam");
+    return 1;
+  }
   g_tuning[key] = value;
   return 0;
 }

@@ -227,18 +227,13 @@ static inline int fwd2_cfg(const GemmBatch& gb) {
 }
 
 // Backward batches at large batch go to gemm_bwdp.hip (LDS-DMA pipelined,
-// cfg 9 = 128x64 tiles, 10 = 64x64, 11 = 128x128, 12 = 64x64 on a 2-stage ring).
+// kCfgBwdp: 64x64 tiles on a 2-stage ring).  64x64 tiles beat 128x64 on every
+// backward launch of the B=4096 SAC step (tools/micro/bwd_micro: critic layer
+// 1 48.8 -> 38.6 us, layer 0 dW 37.9 -> 33.0, -min Q dX 20.7 -> 19.0), and on
+// a 2-stage ring (36 KB of LDS, four workgroups per CU instead of three,
+// bitwise the same) critic layer 0 dW 33.6 -> 30.2, layer 1 38.7 -> 37.8, the
+// rest equal (round 3)
 bool gemm_bwdp_supports(const GemmBatch& b);
-static inline int bwdp_cfg(const GemmBatch& gb) {
-  // 64x64 tiles beat 128x64 on every backward launch of the B=4096 SAC step
-  // (tools/micro/bwd_micro: critic layer 1 48.8 -> 38.6 us, layer 0 dW 37.9
-  // -> 33.0, -min Q dX 20.7 -> 19.0), and on a 2-stage ring (cfg 12: 36 KB of
-  // LDS, four workgroups per CU instead of three, bitwise the same) critic
-  // layer 0 dW 33.6 -> 30.2, layer 1 38.7 -> 37.8, the rest equal (round 3)
-  const int forced = tuning(OAC_TUNE_BWDP_CFG);
-  (void)gb;
-  return (forced >= 9 && forced <= 17 && forced != 16) ? forced : 12;
-}
 
 static inline int launch_cfg(int cfg, const GemmBatch& gb) {
   if (cfg == 0) return 0;
@@ -265,7 +260,7 @@ static inline int launch_cfg(int cfg, const GemmBatch& gb) {
   // along with its batch's dW (same-box A/B, B=4096: SAC 3,276 -> 3,310,
   // configs[4] 4,106 -> 4,200 steps/s against keeping those batches on the
   // register-direct kernel of the time)
-  if (all_bwd && gemm_bwdp_supports(gb)) return bwdp_cfg(gb);
+  if (all_bwd && gemm_bwdp_supports(gb)) return kCfgBwdp;
   // the rest (hidden < 64, ragged dims, mixed batches): the LDS-tiled kernel,
   // or the small kernel for a batch carrying the width-1 head dot (an
   // epilogue the LDS-tiled kernel does not have)

@@ -59,7 +59,7 @@ enum SWs {
   S_DHEAD,
   S_COUNT
 };
-static_assert(S_COUNT <= WS_TICKETS, "workspace ids");
+static_assert(S_COUNT <= WS_GSLAB_Q, "workspace ids");
 
 int sac_shallow_ws_alias(int which) { return which == OAC_WS_H1P ? (int)S_H1P : which; }
 

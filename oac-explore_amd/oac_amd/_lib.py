@@ -9,7 +9,7 @@ import os
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 # OAC_LIB: another in-tree build of the same library (same-box A/B runs of a
-# kernel change, e.g. tools/ab_lib.sh); the default is the package's own
+# kernel change); the default is the package's own
 _DEFAULT_LIB = os.path.join(HERE, "liboac_amd.so")
 LIB_PATH = os.environ.get("OAC_LIB") or _DEFAULT_LIB
 
@@ -30,7 +30,7 @@ OAC_DP_OVERLAP = 2
 
 # oac_sac_trace bits
 TRACE = dict(direct=1, direct_big=2, batch_copy=4, qdot=8, wl_targets=16, split_phase1=32,
-             fused=64, exchange=128, la_adam=256, head_dh2=512)
+             fused=64, exchange=128, head_dh2=512)
 
 # oac_allreduce_fn: int (*)(void* ctx, float* buf, int64_t n, void* stream)
 ALLREDUCE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
@@ -42,12 +42,12 @@ WS = {name: i for i, name in enumerate([
     "q1", "q2", "qn1", "qn2", "tq1", "tq2", "y", "sqe1", "sqe2", "qnew", "counts",
     "head3", "act3", "logp_part", "h2q1", "h2q2", "h1p", "h2p"])}
 # non-default kernel / schedule choices (enum oac_tuning_key; A/B runs and the
-# alternative-kernel parity tests): set_tuning(bwdp_cfg=9, ...) before the
+# alternative-kernel parity tests): set_tuning(fwd_tile_m=128, ...) before the
 # trainers that should use them create their plans; 0 restores a default
 TUNE = {name: i for i, name in enumerate([
-    "bwdp_cfg", "fwd_tile_m", "fwd_tile_n", "fwd_nb", "split_adam", "dh2_targets", "head_cc",
+    "retired_0", "fwd_tile_m", "fwd_tile_n", "fwd_nb", "split_adam", "dh2_targets", "head_cc",
     "splits_q1", "splits_q0", "splits_ph", "splits_p1", "splits_p0", "debug_cfg",
-    "ring_direct", "ring_prefetch", "la_adam", "head_dh2"])}
+    "ring_direct", "ring_prefetch", "retired_15", "head_dh2"])}
 
 
 def set_tuning(**kw):

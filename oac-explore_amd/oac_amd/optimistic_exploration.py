@@ -12,7 +12,6 @@ sequence, each row exactly as a single call.  ``policy`` must be the policy of a
 place); there is no torch/CPU fallback.
 """
 import ctypes
-import os
 
 import numpy as np
 import torch
@@ -70,7 +69,7 @@ def get_optimistic_exploration_action(ob_np, policy=None, qfs=None, trainer=None
     if deterministic:
         raise NotImplementedError("the deterministic OAC variant is unreachable from rollout() "
                                   "(SURVEY 8a quirk Q7) and not implemented")
-    if eps is None and not return_info and not _USE_GRAPH:
+    if eps is None and not return_info:
         return _action_now(ob_np, policy, qfs, trainer, hyper_params), {}
     assert np.ndim(ob_np) == 1
     t = _owner(policy, qfs, trainer, hyper_params)
@@ -146,15 +145,10 @@ def get_optimistic_exploration_actions(obs_np, policy=None, qfs=None, trainer=No
                     trainer is not None)
 
 
-_USE_GRAPH = os.environ.get("OAC_EXPL_GRAPH", "0") == "1"
-
-
 def _actions(t, obs, hyper_params, eps, return_info, trainer_ub=False):
     """One launch on torch's current stream: the kernel reads the observations
     from and writes the results to the handle's host-coherent staging, and the
-    call returns when its completion word lands (oac_expl_action_now).
-    OAC_EXPL_GRAPH=1: the captured-graph path instead (oac_expl_action: upload,
-    kernel and download replayed, then a stream synchronisation)."""
+    call returns when its completion word lands (oac_expl_action_now)."""
     n = obs.shape[0]
     e = t._expl_handle(n)
     if t.layout.q2_base < 0:   # K heads: mean + beta std, or trainer.predict's sorted head
@@ -169,12 +163,7 @@ def _actions(t, obs, hyper_params, eps, return_info, trainer_ub=False):
         e.eps.copy_(torch.from_numpy(np.ascontiguousarray(eps, np.float32)).reshape(e.eps.shape))
         ed = e.eps
     beta, delta = float(hyper_params["beta_UB"]), float(hyper_params["delta"])
-    if _USE_GRAPH:
-        check(_lib.lib().oac_expl_action(e.handle, ptr(ed), beta, delta, None, None, None, None,
-                                         stream_ptr(s)))
-        s.synchronize()
-    else:
-        check(_lib.lib().oac_expl_action_now(e.handle, ptr(ed), beta, delta, stream_ptr(s)))
+    check(_lib.lib().oac_expl_action_now(e.handle, ptr(ed), beta, delta, stream_ptr(s)))
     res = e.out_np
     info = {}
     if return_info:

@@ -45,7 +45,7 @@ def main(out):
                          soft_target_tau=5e-3, use_automatic_entropy_tuning=True)
         for k, v in _run(sac, Do, Da, B, 11).items():
             res[f"sac_{H}_{k}"] = v
-        # the step's trace bits (not compared: the parent checks the path taken)
+        # the step's trace bits (printed, not compared)
         trace[f"sac_{H}"] = _lib.lib().oac_sac_trace(sac._last_plan.handle, 1)
         K = 7
         pp, qp = producers(sac_params(Do, Da, [H, H], 3, q_out=K, pi_init_w=0.2, q_init_w=0.1,

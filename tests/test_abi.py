@@ -146,6 +146,28 @@ def test_tuning_keys_match_the_header_and_reject_unknown():
     assert b"tuning key" in L.oac_last_error()
 
 
+def test_retired_tuning_keys_are_refused_by_name():
+    """The two retired keys (once the backward tile configuration and the
+    last-arrival Adam) refuse a non-zero value with a message that names the
+    removal, instead of ignoring an old caller's choice; 0 is accepted, so a
+    loop that resets every key keeps working; one past the end is still
+    rejected (host-only: no GPU call)."""
+    from oac_amd import _lib
+    L = _lib.lib()
+    retired = [n for n in _header_enum("OAC_TUNE_", "OAC_TUNE_COUNT") if "RETIRED" in n]
+    assert retired == ["OAC_TUNE_RETIRED_0", "OAC_TUNE_RETIRED_15"]
+    for name in retired:
+        key = _lib.TUNE[name[len("OAC_TUNE_"):].lower()]
+        assert key == int(name.rsplit("_", 1)[1])
+        for value in (9, 1, -1):
+            assert L.oac_tuning_set(key, value) != 0, (name, value)
+            msg = L.oac_last_error()
+            assert name.encode() in msg and b"removed" in msg and b"one configuration" in msg, msg
+        assert L.oac_tuning_set(key, 0) == 0, name
+    assert L.oac_tuning_set(len(_lib.TUNE), 0) != 0
+    assert b"unknown tuning key" in L.oac_last_error()
+
+
 def test_trace_bits_match_the_header():
     """oac_amd._lib.TRACE carries every OAC_TRACE_* bit the header defines."""
     from oac_amd import _lib

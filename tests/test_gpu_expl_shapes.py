@@ -219,31 +219,6 @@ def test_group_size_sweep(name, n):
             assert _bits_equal(got[k][r], single[k][j]), (name, n, k, "row", r)
 
 
-@pytest.mark.parametrize("name", ["23x6x250-d0.5", "300x19x256-d0.5", "23x6x250x7-mean-d0.5"])
-def test_captured_graph_path_is_bitwise_the_direct_one(name):
-    """OAC_EXPL_GRAPH (oe._USE_GRAPH): one twin, one split-twin, one K-head case."""
-    from oac_amd import get_optimistic_exploration_action, get_optimistic_exploration_actions
-    from oac_amd import optimistic_exploration as oe
-    case = ec.BY_NAME[name]
-    tr = trainer_for(case)
-    obs, eps = ec.inputs(case)
-    kw = _call_kw(case, tr)
-    assert not oe._USE_GRAPH
-    A, info = get_optimistic_exploration_actions(obs, eps=eps, return_info=True, **kw)
-    a0, info0 = get_optimistic_exploration_action(obs[3], eps=eps[3], return_info=True, **kw)
-    oe._USE_GRAPH = True
-    try:
-        Ag, infog = get_optimistic_exploration_actions(obs, eps=eps, return_info=True, **kw)
-        ag, infog0 = get_optimistic_exploration_action(obs[3], eps=eps[3], return_info=True, **kw)
-    finally:
-        oe._USE_GRAPH = False
-    assert _bits_equal(Ag, A) and _bits_equal(ag, a0)
-    for k in ("mu_E", "std"):
-        assert _bits_equal(infog[k], info[k]) and _bits_equal(infog0[k], info0[k]), k
-    compare(case, dict(action=Ag, mu_E=infog["mu_E"], std=infog["std"],
-                       grad=run(case, tr, obs, eps)["grad"]), list(range(case.n)), "graph")
-
-
 @pytest.mark.parametrize("name,obs_arg", [("513x4x64-d0.5", 0), ("300x19x256-d0.5", 1)])
 def test_single_call_philox_path_split_kernel(name, obs_arg):
     """The eps-free single call with twin critics in the split kernel: at

@@ -219,7 +219,7 @@ def test_exploration_group_sizes_and_paths_bitwise(n):
     single-observation call, the golden rows stay within tolerance, and the
     captured-graph path (oac_expl_action) equals the direct one."""
     from oac_amd import get_optimistic_exploration_action, get_optimistic_exploration_actions
-    from oac_amd import optimistic_exploration as oe
+    from oac_amd import _lib as L
     meta, g = parity.load("oac_expl_humanoid")
     params = sac_params(meta["obs_dim"], meta["act_dim"], meta["hidden"], meta["seed"],
                         pi_init_w=meta["pi_init_w"], q_init_w=meta["q_init_w"])
@@ -228,6 +228,20 @@ def test_exploration_group_sizes_and_paths_bitwise(n):
              seed=meta["seed"], pi_init_w=meta["pi_init_w"], q_init_w=meta["q_init_w"])
     tr = sac_trainer_for(m, params=params)
     hp = dict(beta_UB=meta["beta_UB"], delta=meta["delta"], share_layers=False)
+
+    def graph_action(rows):
+        """oac_expl_action on the handle the last call of `rows` observations
+        used (its staging holds that call's observations, its eps slot that
+        call's eps): the action the replayed download leaves in the staging."""
+        e = tr._expl_handle(rows)
+        s = torch.cuda.current_stream(tr.device)
+        e.out_np[0].fill(np.nan)
+        L.check(L.lib().oac_expl_action(e.handle, L.ptr(e.eps), float(hp["beta_UB"]),
+                                        float(hp["delta"]), None, None, None, None,
+                                        L.stream_ptr(s)))
+        s.synchronize()
+        return e.out_np[0].copy()
+
     k = meta["n_obs"]
     rs = np.random.RandomState(n)
     obs = np.concatenate([g["obs"], rs.standard_normal((n - k, meta["obs_dim"]))])
@@ -235,6 +249,7 @@ def test_exploration_group_sizes_and_paths_bitwise(n):
     A, info = get_optimistic_exploration_actions(obs, policy=tr.policy, qfs=tr.qfs,
                                                  hyper_params=hp, eps=eps, return_info=True)
     assert np.isfinite(A).all()
+    np.testing.assert_array_equal(graph_action(n), A)
     for i in range(k):
         assert parity.rel_err(A[i], g["action"][i]) <= parity.TOL
         assert parity.rel_err(info["mu_E"][i], g["mu_E"][i]) <= parity.TOL
@@ -242,16 +257,10 @@ def test_exploration_group_sizes_and_paths_bitwise(n):
         a, _ = get_optimistic_exploration_action(obs[i], policy=tr.policy, qfs=tr.qfs,
                                                  hyper_params=hp, eps=eps[i])
         np.testing.assert_array_equal(a, A[i])
-    oe._USE_GRAPH = True
-    try:
-        Ag, _ = get_optimistic_exploration_actions(obs, policy=tr.policy, qfs=tr.qfs,
-                                                   hyper_params=hp, eps=eps)
-        a0, _ = get_optimistic_exploration_action(obs[3], policy=tr.policy, qfs=tr.qfs,
-                                                  hyper_params=hp, eps=eps[3])
-    finally:
-        oe._USE_GRAPH = False
-    np.testing.assert_array_equal(Ag, A)
-    np.testing.assert_array_equal(a0, A[3])
+    a3, _ = get_optimistic_exploration_action(obs[3], policy=tr.policy, qfs=tr.qfs,
+                                              hyper_params=hp, eps=eps[3])
+    np.testing.assert_array_equal(a3, A[3])
+    np.testing.assert_array_equal(graph_action(1)[0], A[3])
     c0 = int(tr.step_state[2].item())
     A2, _ = get_optimistic_exploration_actions(obs, policy=tr.policy, qfs=tr.qfs, hyper_params=hp)
     assert np.isfinite(A2).all() and np.abs(A2).max() <= 1   # random rows may saturate tanh

@@ -1,5 +1,5 @@
 #!/bin/bash
-# Copy the summaries of a tools/measure_r4.sh run (gpurun_out/) into profiles/<round>/
+# Copy the summaries of a tools/measure_r5.sh run (its output directory) into profiles/<round>/
 # and refresh profiles/pmc_gemm_traffic.json (read by bench.py's roofline.traffic).
 set -e
 R=${1:-r04}

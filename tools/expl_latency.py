@@ -42,11 +42,6 @@ def main():
     ob = np.random.RandomState(0).standard_normal(Do)
     full = bench(lambda: oac_amd.get_optimistic_exploration_action(ob, policy=tr.policy,
                                                                    qfs=tr.qfs, hyper_params=hp))
-    from oac_amd import optimistic_exploration as oe
-    oe._USE_GRAPH = True
-    full_graph = bench(lambda: oac_amd.get_optimistic_exploration_action(
-        ob, policy=tr.policy, qfs=tr.qfs, hyper_params=hp))
-    oe._USE_GRAPH = False
     e = tr._expl_handle(1)
     L = _lib.lib()
     s = tr.stream
@@ -72,7 +67,7 @@ def main():
     t_kernel = bench(launch)
     check(L.oac_expl_host_staging(e.handle, ctypes.byref(po), ctypes.byref(pr)))
     check(L.oac_expl_set_host_io(e.handle, po, pr))
-    print({"full_call_us": round(full, 1), "full_call_graph_us": round(full_graph, 1),
+    print({"full_call_us": round(full, 1),
            "action_now_us": round(t_now, 1), "call_64obs_us": round(t64, 1), "graph_with_host_io_sync_us": round(t_launch, 1),
            "graph_device_only_sync_us": round(t_kernel, 1),
            "tiny_kernel_sync_us": round(t_tiny, 1)})

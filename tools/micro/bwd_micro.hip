@@ -1,9 +1,9 @@
 // Large-batch backward GEMM launches of the B=4096 SAC step (Humanoid dims:
 // critic layer 1 dW + last-layer dW + rank-1-seeded dX, critic layer 0 dW,
 // the -min Q dX pair, policy layer 1 dW + dX, policy layer 0 dW) through
-// gemm_batch_launch on the LDS-DMA pipelined
-// gemm_bwdp.hip (cfg 9 / 10 / 11 or OAC_BWDP_CFG): per-launch time and the
-// largest norm-relative difference of every output.  Build: tools/micro/Makefile.
+// gemm_batch_launch on the LDS-DMA pipelined gemm_bwdp.hip (cfg 12) against
+// the LDS-tiled kernel (cfg 1): per-launch time and the largest norm-relative
+// difference of every output.  Build: tools/micro/Makefile.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cmath>
@@ -26,7 +26,7 @@ using namespace oac;
 static void clocks(const GemmBatch& b0, int cfg, hipStream_t s) {
   GemmBatch b = b0;
   gemm_batch_finalize(b, cfg);
-  CK(gemm_bwdp_launch(b, cfg, s));
+  CK(gemm_bwdp_launch(b, s));
   CK(hipStreamSynchronize(s));
   print_pipe_clocks(b.total_tiles);
 }
@@ -100,8 +100,8 @@ static std::vector<std::vector<float>> snap() {
 }
 
 int main(int argc, char** argv) {
-  const int cfg_new = argc > 1 ? atoi(argv[1]) : 9;
-  const int cfg_ref = argc > 2 ? atoi(argv[2]) : 3;   // reference kernel (outputs and time)
+  const int cfg_new = argc > 1 ? atoi(argv[1]) : 12;
+  const int cfg_ref = argc > 2 ? atoi(argv[2]) : 1;   // reference kernel (outputs and time)
   const int B = 4096, Do = 376, Da = 17, H = 256, Dq = Do + Da, RS = 772;
   hipStream_t s; CK(hipStreamCreate(&s));
   float* X = dev_rand((size_t)B * RS, 1);
