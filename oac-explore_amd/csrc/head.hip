@@ -100,10 +100,14 @@ __global__ void __launch_bounds__(64 * kHeadWaves) policy_head_kernel(const Head
 #pragma unroll
     for (int j = 0; j < kC; ++j)
       if (c0 + j * kHeadWaves < chunks) {
+        // element c of the loaded vector is k = kl + c at the offset head_loads
+        // used; a clamped load (H % 4 != 0: the row's tail) overlaps the lane
+        // group before it, and only its k >= kb are this group's
         const int kb = 16 * (c0 + j * kHeadWaves) + 4 * g4;
+        const int kl = min(kb, H - 4);
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
-          const bool kin = kb + c < H;
+          const bool kin = kl + c >= kb;
           const float av = kin ? xa[j][c] : 0.f;
 #pragma unroll
           for (int t = 0; t < 4; ++t)

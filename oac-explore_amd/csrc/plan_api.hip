@@ -266,6 +266,11 @@ static int validate(const oac_sac_config* c) {
               "activations as float4 columns), got %d", c->hidden);
     return 1;
   }
+  if (c->n_hidden != 1 && c->hidden >= 1 && c->hidden < 4) {   // (hidden < 1: "bad dims" below)
+    set_error("n_hidden = 2: hidden must be at least 4 (the policy head kernel reads the hidden "
+              "activations as float4 columns), got %d", c->hidden);
+    return 1;
+  }
   if (c->global_opt != 0 && c->global_opt != 1) {
     set_error("global_opt must be 0 or 1, got %d", c->global_opt);
     return 1;

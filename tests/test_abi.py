@@ -99,6 +99,38 @@ def test_every_kind_has_a_layout_and_its_views_fit_the_workspace(kind, q_out):
         assert L.oac_sac_destroy(h) == 0
 
 
+@pytest.mark.parametrize("kind,q_out", [(0, 1), (1, 10), (2, 2), (3, 10), (4, 1)])
+def test_two_hidden_layers_refuse_a_width_below_4_by_name(kind, q_out):
+    """The policy head kernel (csrc/head.hip) reads the hidden activations as
+    float4 columns clamped to hidden - 4: any width from 4 is served, a
+    narrower one is refused when the layout is queried and when the plan is
+    created, before any buffer is touched."""
+    from oac_amd import _lib, row_layout
+    L = _lib.lib()
+
+    def cfg_for(H, n_hidden):
+        cfg = _lib.SacConfig()
+        cfg.kind, cfg.obs_dim, cfg.act_dim, cfg.hidden, cfg.q_out, cfg.batch = kind, 11, 3, H, q_out, 40
+        for k, v in row_layout(11, 3).items():
+            setattr(cfg, k, v)
+        cfg.gemm_cfg, cfg.world_size, cfg.n_hidden = -1, 1, n_hidden
+        return cfg
+
+    for n_hidden in (0, 2):
+        for H in (1, 2, 3):
+            cfg, lay = cfg_for(H, n_hidden), _lib.SacLayout()
+            assert L.oac_sac_query_layout(ctypes.byref(cfg), ctypes.byref(lay)) != 0, (H, n_hidden)
+            msg = L.oac_last_error()
+            for w in (b"n_hidden = 2", b"hidden must be at least 4", b"got %d" % H):
+                assert w in msg, (w, msg)
+            h, bufs = ctypes.c_void_p(), _lib.SacBuffers()
+            assert L.oac_sac_create(ctypes.byref(cfg), ctypes.byref(bufs), ctypes.byref(h)) != 0
+            assert not h.value and b"at least 4" in L.oac_last_error()
+        for H in (4, 5, 30, 513):   # every width from 4, ragged ones included
+            cfg, lay = cfg_for(H, n_hidden), _lib.SacLayout()
+            assert L.oac_sac_query_layout(ctypes.byref(cfg), ctypes.byref(lay)) == 0, L.oac_last_error()
+
+
 def test_row_layout_keeps_critic_input_contiguous():
     from oac_amd import row_layout
     r = row_layout(376, 17)

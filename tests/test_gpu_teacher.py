@@ -73,28 +73,28 @@ def _load_alpha(orc, tr):
     orc.n_steps = tr._n_train_steps_total
 
 
-def sac_oracle_from_gpu(tr, meta):
+def sac_oracle_from_gpu(tr, meta, dtype=torch.float32):
     """The fp32 oracle holding the GPU SAC trainer's current state."""
     params = {g: _np_sd(getattr(tr, g))
               for g in ("policy", "qf1", "qf2", "target_qf1", "target_qf2")}
     orc = so.SACOracle(params, meta["obs_dim"], meta["act_dim"], discount=meta["discount"],
                        reward_scale=meta["reward_scale"], policy_lr=meta["lr"],
                        qf_lr=meta["lr"], tau=meta["tau"], auto_alpha=meta["auto_alpha"],
-                       target_update_period=meta.get("target_update_period", 1))
+                       target_update_period=meta.get("target_update_period", 1), dtype=dtype)
     for opt, mod in ((orc.opt_p, tr.policy), (orc.opt_q1, tr.qf1), (orc.opt_q2, tr.qf2)):
         _load_adam(opt, tr, mod)
     _load_alpha(orc, tr)
     return orc
 
 
-def poac_oracle_from_gpu(tr, meta):
+def poac_oracle_from_gpu(tr, meta, dtype=torch.float32):
     params = {"policy": _np_sd(tr.policy), "qf1": _np_sd(tr.qfs[0]),
               "target_qf1": _np_sd(tr.tfs[0])}
     orc = so.ParticleOACOracle(params, meta["obs_dim"], meta["act_dim"], meta["K"],
                                discount=meta["discount"], policy_lr=meta["lr"],
                                qf_lr=meta["lr"], tau=meta["tau"],
                                target_update_period=meta.get("target_update_period", 1),
-                               train_bias=meta.get("train_bias", True))
+                               train_bias=meta.get("train_bias", True), dtype=dtype)
     _load_adam(orc.opt_p, tr, tr.policy)
     _load_adam(orc.opt_q, tr, tr.qfs[0])
     _load_alpha(orc, tr)
