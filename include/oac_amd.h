@@ -226,6 +226,56 @@ int oac_sac_create(const oac_sac_config* cfg, const oac_sac_buffers* bufs, oac_s
 int oac_sac_destroy(oac_sac* h);
 int oac_sac_step(oac_sac* h, int flags, void* stream);
 
+/* Policy ensemble: ParticleTrainer(ensemble=True, n_policies=P) without
+ * share_layers (particle_trainer.py:115-137, policies.py:546-647) -- P
+ * separately optimised deterministic policies; the TD target's next action is,
+ * per row, the proposal a'_p = tanh(mean_p(next_obs)) with the largest
+ * UB_p = sort_k(q_k(next_obs, a'_p))[delta_index] under the K ONLINE, pre-step
+ * critics (the first maximum wins; with mean_update the target policy acts and
+ * nothing is selected); policy p alone ascends mean(UB_p) of the post-step
+ * critics on obs; target policy, critics and Polyak as without the ensemble.
+ *
+ * The P policies are stored STACKED, as `unshared` stores the critics: one
+ * policy block of hidden width P * hidden holding fc0.weight [P * hidden,
+ * obs_dim], fc0.bias [P * hidden], the heads [P, 2 * act_dim, hidden]
+ * (block-diagonal over the P hidden segments; rows 0..Da-1 of a policy's slice
+ * = last_fc.weight, Da..2Da-1 = last_fc_log_std.weight) and their biases
+ * [P, 2 * act_dim]; policy p's tensors are slice p of each, contiguous.  The
+ * arenas are [policy block | target_policy | critic block]: the target policy
+ * keeps a single policy's shape (oac_sac_layout pol_* offsets from tpol_base),
+ * tpol_base = ens_size, q1_base = ens_size + pol_size, and one Adam group of
+ * q1_base floats runs over [policy block | target_policy].
+ *
+ * Valid: kind PARTICLE_UB, unshared == 1, n_hidden == 1, world_size == 1,
+ * global_opt == 0, hidden % 4 == 0, 1 <= n_policies <= 16 and
+ * buffers.next_policy == NULL; anything else fails with a message that names
+ * the field and the kind.  The step's kernels put no further bound on
+ * n_policies * hidden or q_out * hidden (they keep nothing of that size in
+ * LDS).  n_policies == 0 is the plain call (oac_sac_query_layout /
+ * oac_sac_create; *ens zeroed).  An ensemble handle rejects OAC_STEP_USE_GRAPH,
+ * oac_sac_step_phase and oac_sac_set_allreduce by name; its step's launch
+ * count does not depend on n_policies. */
+typedef struct oac_ensemble_layout {
+  int64_t n_policies;
+  /* the stacked policy block, float offsets in the arenas */
+  int64_t ens_fc0_w, ens_fc0_b, ens_head_w, ens_head_b, ens_size;
+  /* the target_policy block's tensors, from tpol_base (= oac_sac_layout pol_*) */
+  int64_t tpol_fc0_w, tpol_fc0_b, tpol_head_w, tpol_head_b, tpol_size;
+} oac_ensemble_layout;
+int oac_sac_query_layout_ensemble(const oac_sac_config* cfg, int n_policies, oac_sac_layout* out,
+                                  oac_ensemble_layout* ens);
+int oac_sac_create_ensemble(const oac_sac_config* cfg, int n_policies, const oac_sac_buffers* bufs,
+                            oac_sac** out);
+/* Workspace views of an ensemble handle (as oac_sac_workspace_view; values of
+ * the last step): the chosen policy per next_obs row as a float [B, 1] and
+ * every UB_p of the selection [B, P] (0 rows with mean_update), the P actions
+ * and heads on obs [B, P * Da] / [B, P * 2 Da], every policy's phase-2 upper
+ * bound [B, P] (OAC_WS_QNEW holds policy P-1's). */
+enum oac_ens_view {
+  OAC_ENS_SEL = 0, OAC_ENS_UB_NEXT, OAC_ENS_ACT, OAC_ENS_HEAD, OAC_ENS_UB_OBS, OAC_ENS_VIEW_COUNT
+};
+int oac_sac_ensemble_view(oac_sac* h, int which, int64_t* offset, int64_t* rows, int64_t* cols);
+
 /* n_steps consecutive steps (each its own minibatch from the device index
  * ring, exactly as n calls of oac_sac_step); with OAC_STEP_USE_GRAPH they are
  * captured into one graph, so the per-launch host/graph cost is paid once per
@@ -581,6 +631,28 @@ int oac_policy_eval_fixed_std(const float* net, const int64_t* offsets, int obs_
                               const float* std_dev, const float* eps, float* action, float* mean,
                               float* log_std, float* log_prob, float* std_out, float* pre_tanh,
                               void* stream);
+
+/* EnsemblePolicy.forward / get_action (trainer/policies.py:576-631) for n
+ * observations in ONE stream-ordered launch, no host synchronisation: the P
+ * stacked policies (pol_offsets = {fc0.weight, fc0.bias, heads, head biases} of
+ * the stacked block inside `policies`: oac_ensemble_layout ens_*) propose
+ * a_p = tanh(mean_p) -- or, with noise [n, P, act_dim] standard normals,
+ * tanh(mean_p + std_p * noise_p) -- the K stacked critics (q_offsets =
+ * {fc0.weight, fc0.bias, last_fc.weight, last_fc.bias} inside `critics`:
+ * oac_sac_layout q_fc0_w, q_fc0_b, q_last_w, q_last_b of an unshared layout)
+ * give UB_p = sort_k(q_k(obs, a_p))[delta_index], and the first maximum is
+ * chosen -- the device function the step's selection kernel runs.  Outputs:
+ * chosen [n] (int32), ub [n, P], and the chosen policy's forward outputs
+ * action, mean, log_std (clamped), std, pre_tanh [n, act_dim] and log_prob [n]
+ * (may be NULL; 0 without noise).  A workgroup keeps obs_dim + (P + K) * hidden
+ * floats in dynamic LDS, at most 128 KiB; more is refused by name before any
+ * launch.  act_dim <= 32. */
+int oac_ensemble_eval(const float* policies, const int64_t* pol_offsets, int n_policies,
+                      const float* critics, const int64_t* q_offsets, int n_critics,
+                      int delta_index, int obs_dim, int act_dim, int hidden, const float* obs,
+                      int64_t ld_obs, int n, const float* noise, int32_t* chosen, float* ub,
+                      float* action, float* mean, float* log_std, float* log_prob, float* std_out,
+                      float* pre_tanh, void* stream);
 
 /* ---------------------------------------------------------------- errors */
 const char* oac_last_error(void);

@@ -73,9 +73,24 @@ enum GWs {
   G_PN, G_H1N, G_H2N, G_PN3, G_H1N3, G_H2N3, G_GQ, G_GQ3, G_DH2N, G_DH1N, G_DH2N3, G_DH1N3,
   G_DA, G_DA3, G_DHEAD, G_DHEAD3, G_DH2P, G_DH1P, G_DH2TP, G_DH1TP,
   G_OPT,   // global_opt sweep: per-workgroup partials of the history row, then the ticket word
+  // policy ensemble (SacPlan::n_policies): the stacked policies' layer 0 on obs /
+  // next_obs and its gradient [B, P H], the online critics' projection of
+  // next_obs [B, K H], the P heads / actions on obs and their gradients, the
+  // chosen index per next_obs row, the selection's and phase 2's UB_p [B, P]
+  G_EH1, G_EH2, G_EDH1, G_EPQ, G_EHEAD, G_EACT, G_EDHEAD, G_ESEL, G_EUB2, G_EUB1,
   G_COUNT
 };
 static_assert(G_COUNT <= WS_GSLAB_Q, "workspace ids");
+
+int det_ens_view(int which) {
+  switch (which) {
+    case OAC_ENS_SEL: return G_ESEL;
+    case OAC_ENS_UB_NEXT: return G_EUB2;
+    case OAC_ENS_ACT: return G_EACT;
+    case OAC_ENS_HEAD: return G_EHEAD;
+    default: return G_EUB1;
+  }
+}
 
 void det_layout_workspace(SacPlan& p) {
   const oac_sac_config& c = p.c;
@@ -98,6 +113,15 @@ void det_layout_workspace(SacPlan& p) {
   for (int id : {G_DA, G_DA3}) set(id, B, Da);
   for (int id : {G_DHEAD, G_DHEAD3}) set(id, B, 2 * Da);
   if (c.global_opt) set(G_OPT, 1, 2 * kPolicyOptMaxBlocks + 64);
+  if (p.n_policies) {
+    const int64_t P = p.n_policies;
+    for (int id : {G_EH1, G_EH2, G_EDH1}) set(id, B, P * H);
+    set(G_EPQ, B, q_hidden(p));
+    set(G_EHEAD, B, P * 2 * Da); set(G_EDHEAD, B, P * 2 * Da);
+    set(G_EACT, B, P * Da);
+    set(G_EUB1, B, P);
+    if (!c.mean_update) { set(G_ESEL, B, 1); set(G_EUB2, B, P); }
+  }
   finish_layout(p);
 }
 
@@ -427,10 +451,186 @@ static int dphase2(SacPlan& p, hipStream_t s, bool fused) {
   return 0;
 }
 
+// ------------------------------------------------------- policy ensemble
+// ParticleTrainer(ensemble=True) without share_layers (SacPlan::n_policies =
+// P > 0; unshared critics, one hidden layer): the depth-1 unshared chain with
+// the P stacked policies in the policy's place.  What the policies share is
+// computed once -- layer 0 of all of them is one product of width P H, the
+// critics' projection of the rows one product of width K H -- and what differs
+// per policy is row work (ensemble.hip), so the launch count does not depend on
+// P: gather / counts, then
+//   0  layer 0: stacked policies (obs), stacked policies (next_obs) | target
+//      policy (next_obs, mean_update), target policy (obs), critics (obs, a),
+//      target critics' projection, online critics' projection (next_obs; not
+//      with mean_update)                                      <= 6 tasks
+//   1  head launch: target policy on obs (+ on next_obs with the target
+//      critics' action columns, mean_update)
+//   2  ens_select: the P heads on obs; selection on next_obs -> a'_{p*}, the
+//      target critics' hidden layer (not with mean_update)
+//   3-5 phase 1, unchanged (targets, layer-0 dW, last layer + critic Adam)
+//   6  post-step critics' layer 0 on (obs, a~_T); its projection serves all P
+//   7  det_seed_head_backward, the target policy's segment
+//   8  ens_seed: per (row, policy) UB_p, seed, da_p, dhead_p, heads' dX
+//   9  target policy's head dW / dX
+//   10 ens_head_dw: the block-diagonal heads' dW / db
+//   11 layer-0 dW of the stacked policies and the target policy (+ the group's
+//      Adam in the epilogue when can_fuse_adam; else 12: run_adam)
+static EnsNets ens_nets(SacPlan& p, const float* q) {
+  const oac_sac_config& c = p.c;
+  EnsNets n;
+  std::memset(&n, 0, sizeof(n));
+  n.wh = p.b.params + p.E.ens_head_w; n.bh = p.b.params + p.E.ens_head_b;
+  n.wa = q + p.L.q_fc0_w + c.obs_dim; n.ld_wa = c.obs_dim + c.act_dim;
+  n.wl = q + p.L.q_last_w; n.bl = q + p.L.q_last_b;
+  n.P = p.n_policies; n.K = c.q_out; n.H = c.hidden; n.Da = c.act_dim; n.delta_index = c.delta_index;
+  return n;
+}
+// layer 0 of the P stacked policies on the rows' columns x: h1 [B, P H]
+static GemmTask ens_l0(SacPlan& p, const float* x, int h1) {
+  const oac_sac_config& c = p.c;
+  const int PH = p.n_policies * c.hidden;
+  return t_fwd(x, c.row_stride, c.batch, c.obs_dim, p.b.params + p.E.ens_fc0_w, c.obs_dim, PH, p.W(h1),
+               PH, EPI_BIAS_RELU, p.b.params + p.E.ens_fc0_b);
+}
+static GemmTask ens_l0_dw(SacPlan& p, int dh1) {
+  const oac_sac_config& c = p.c;
+  const int PH = p.n_policies * c.hidden;
+  float* g = grad_p(p);
+  return t_dw(p.W(dh1), PH, PH, c.batch, p.X() + c.off_obs, c.row_stride, c.obs_dim,
+              g + p.E.ens_fc0_w, g + p.E.ens_fc0_b, p_group(p), p.sp_p0);
+}
+
+static int ens_phase0(SacPlan& p, int flags, hipStream_t s) {
+  const oac_sac_config& c = p.c;
+  const oac_sac_layout& L = p.L;
+  const int B = c.batch, H = c.hidden, Do = c.obs_dim, Da = c.act_dim, RS = c.row_stride;
+  float* X = p.W(OAC_WS_BATCH);
+  const float* obs = X + c.off_obs;
+  const float* nobs = X + c.off_next_obs;
+  if ((flags & OAC_STEP_GATHER) && step_gather(p, flags, s, 0, false)) return 1;
+  if (step_counts(p, flags, s)) return 1;
+  const float* tpol = p.b.params + L.tpol_base;
+  const float* q = p.b.params + L.q1_base;
+  const float* tq = p.b.targets;
+  const bool mu = c.mean_update != 0;
+  {
+    GemmBatch gb{};
+    publish_step(p, gb);
+    add(gb, ens_l0(p, obs, G_EH1));
+    if (mu) add(gb, pol_l0(p, tpol, nobs, G_H1P2));
+    else add(gb, ens_l0(p, nobs, G_EH2));
+    add(gb, pol_l0(p, tpol, obs, G_H1TP));
+    add(gb, critic_l0_rank(p, q, obs, X + c.off_act, RS, G_P, G_H1Q));
+    add(gb, target_proj(p, tq, nobs, G_PT));
+    if (!mu) add(gb, target_proj(p, q, nobs, G_EPQ));   // the ONLINE critics, pre-step
+    if (run_gemm(p, gb, s)) return 1;
+  }
+  {
+    HeadArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.ld_wa = Do + Da; a.det = 1;
+    a.B = B; a.H = H; a.Da = Da;
+    const int Hq = q_hidden(p);
+    a.Hq = Hq;
+    // (column chunks split the target critics' columns: one without mean_update, where no
+    // segment feeds a critic)
+    a.col_chunks = mu ? std::max(1, (Hq + (B >= 1024 ? 127 : 63)) / (B >= 1024 ? 128 : 64)) : 1;
+    HeadSeg& s0 = a.seg[0];   // target_policy(obs) -> a~_T (phase 2)
+    s0.h2 = p.W(G_H1TP); s0.wh = tpol + L.pol_head_w; s0.bh = tpol + L.pol_head_b;
+    s0.head = p.W(OAC_WS_HEAD3); s0.act = p.W(OAC_WS_ACT3);
+    if (mu) {                 // target_policy(next_obs) -> QT(next_obs, a')
+      HeadSeg& s1 = a.seg[1];
+      s1.h2 = p.W(G_H1P2); s1.wh = s0.wh; s1.bh = s0.bh;
+      s1.head = p.W(OAC_WS_HEAD2); s1.act = p.W(OAC_WS_ACT2);
+      s1.n_nets = 1; s1.wa[0] = tq + L.q_fc0_w + Do; s1.pre[0] = p.W(G_PT); s1.h1[0] = p.W(G_H1T);
+    }
+    RUN_ROW(p, s, launch_policy_head(a, mu ? 2 : 1, s));
+  }
+  EnsSelectArgs e;
+  std::memset(&e, 0, sizeof(e));
+  e.n = ens_nets(p, q);
+  e.h1 = p.W(G_EH1); e.head1 = p.W(G_EHEAD); e.act1 = p.W(G_EACT); e.B = B;
+  if (!mu) {
+    e.h2 = p.W(G_EH2); e.pre_q = p.W(G_EPQ); e.sel = p.W(G_ESEL); e.ub2 = p.W(G_EUB2);
+    e.head2 = p.W(OAC_WS_HEAD2); e.act2 = p.W(OAC_WS_ACT2);
+    e.wa_t = tq + L.q_fc0_w + Do; e.pre_t = p.W(G_PT); e.h1t = p.W(G_H1T);
+  }
+  RUN_ROW(p, s, launch_ens_select(e, s));
+  return 0;
+}
+
+static int ens_phase2(SacPlan& p, hipStream_t s, bool fused) {
+  const oac_sac_config& c = p.c;
+  const oac_sac_layout& L = p.L;
+  const int B = c.batch, H = c.hidden, Da = c.act_dim, K = c.q_out;
+  float* X = p.W(OAC_WS_BATCH);
+  const float* q = p.b.params + L.q1_base;   // post-step
+  const long tp = L.tpol_base;
+  {   // (G_PN3: the critics' projection of obs, shared by the P policies' row work)
+    GemmBatch gb{};
+    add(gb, critic_l0_rank(p, q, X + c.off_obs, p.W(OAC_WS_ACT3), Da, G_PN3, G_H1N3));
+    if (run_gemm(p, gb, s)) return 1;
+  }
+  {   // the target policy's loss: the constant seed -1 / (B K) on every critic
+    DetSeedHeadBwdArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.hn = RowHead{p.W(G_H1N), q + L.q_last_w, q + L.q_last_b, p.W(OAC_WS_QN1), q_hidden(p), H};
+    a.h1n1 = p.W(G_H1N3);
+    a.wa = q + L.q_fc0_w + c.obs_dim; a.ld_wa = c.obs_dim + Da;
+    a.act[0] = p.W(OAC_WS_ACT1); a.dhead[0] = p.W(G_DHEAD);   // (segment 0 is not run)
+    a.act[1] = p.W(OAC_WS_ACT3); a.dhead[1] = p.W(G_DHEAD3);
+    a.ub = p.W(OAC_WS_QNEW);
+    a.delta_index = c.delta_index;
+    a.B = B; a.K = K; a.Da = Da;
+    a.seg_lo = 1; a.nseg = 1;
+    RUN_ROW(p, s, launch_det_seed_head_backward(a, s));
+  }
+  {
+    EnsSeedArgs e;
+    std::memset(&e, 0, sizeof(e));
+    e.n = ens_nets(p, q);
+    e.act = p.W(G_EACT); e.pre = p.W(G_PN3); e.h1 = p.W(G_EH1);
+    e.dhead = p.W(G_EDHEAD); e.dh1 = p.W(G_EDH1);
+    e.ub1 = p.W(G_EUB1); e.ub_last = p.W(OAC_WS_QNEW); e.B = B;
+    RUN_ROW(p, s, launch_ens_seed(e, s));
+  }
+  {
+    GemmBatch gb{};
+    add(gb, pol_head_dw(p, tp, G_DHEAD3, G_H1TP));
+    add(gb, pol_head_dx(p, tp, G_DHEAD3, G_DH1TP, G_H1TP));
+    if (run_gemm(p, gb, s)) return 1;
+  }
+  {
+    EnsHeadDwArgs d;
+    std::memset(&d, 0, sizeof(d));
+    d.dhead = p.W(G_EDHEAD); d.h1 = p.W(G_EH1);
+    d.gw = grad_p(p) + p.E.ens_head_w; d.gb = grad_p(p) + p.E.ens_head_b;
+    d.slab_stride = p_group(p); d.S = p.S_p;
+    d.B = B; d.P = p.n_policies; d.H = H; d.Da = Da;
+    RUN_ROW(p, s, launch_ens_head_dw(d, s));
+  }
+  GemmBatch gb{};
+  add(gb, ens_l0_dw(p, G_EDH1));
+  add(gb, pol_l0_dw(p, tp, G_DH1TP));
+  if (fused) {   // [policy block | target_policy] Adam in the epilogue; tail blocks: the heads
+    const long off[2] = {(long)p.E.ens_head_w, (long)(L.tpol_base + L.pol_head_w)};
+    const long n[2] = {(long)(p.E.ens_size - p.E.ens_head_w), (long)(L.pol_size - L.pol_head_w)};
+    fuse_adam(gb, policy_adam(p, 0, nullptr), 2, off, n);
+  }
+  return run_gemm(p, gb, s);
+}
+
 int det_run_step(SacPlan& p, int flags, hipStream_t s, int, int) {
   p.launches = 0;
   const bool fused = can_fuse_adam(p);
   if (fused) p.trace |= OAC_TRACE_FUSED;
+  if (p.n_policies) {
+    if (ens_phase0(p, flags, s)) return 1;
+    if (dphase1(p, flags, s, fused)) return 1;   // (unshared: its last launch steps the critics)
+    if (ens_phase2(p, s, fused)) return 1;
+    if (!fused && run_adam(p, policy_adam(p, 0, nullptr), s)) return 1;
+    return 0;
+  }
   if (dphase0(p, flags, s)) return 1;
   if (dphase1(p, flags, s, fused)) return 1;
   // (unshared: phase 1's last launch has stepped the critic block)

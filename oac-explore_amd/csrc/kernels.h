@@ -356,6 +356,76 @@ struct DetSeedHeadBwdArgs {
 };
 hipError_t launch_det_seed_head_backward(const DetSeedHeadBwdArgs& a, hipStream_t s);
 
+// ----------------------------------------------------------------------------
+// Policy ensemble (ParticleTrainer ensemble=True, share_layers=False, one hidden
+// layer; ensemble.hip).  P policies stored stacked: layer 0 [P H, Do] / [P H],
+// heads [P, 2 Da, H] / [P, 2 Da] (policy p = slice p of each); K one-output
+// critics stacked as RowHead::seg describes.  EnsNets: what the per-row
+// selection reads.
+struct EnsNets {
+  const float* wh; const float* bh;     // stacked heads [P, 2 Da, H], [P, 2 Da]
+  const float* wa; long ld_wa;          // the critic block's action columns W0[:, Do:] (row n at wa + n ld_wa)
+  const float* wl; const float* bl;     // the critics' last layers [K H], [K]
+  int P, K, H, Da, delta_index;
+};
+// Phase 0: the P heads on obs (-> head1 / act1 [B, P, 2 Da] / [B, P, Da]) and,
+// with sel set, on next_obs: per row and policy the K online critics' values
+// from their saved obs projection, the delta_index-th sorted one as UB_p, the
+// first maximum p*; a'_{p*} and its head row go to head2 / act2 and through the
+// target critic block's action columns into h1t = relu(pre_t + a' . wa_t^T).
+struct EnsSelectArgs {
+  EnsNets n;
+  const float* h1; const float* h2;     // [B, P H] stacked layer 0 on obs / next_obs
+  float* head1; float* act1;
+  const float* pre_q;                   // [B, K H] online critics' projection of next_obs (+ bias)
+  float* sel; float* ub2;               // [B] chosen index (as a float), [B, P] UB_p; sel null: obs only
+  float* head2; float* act2;            // [B, 2 Da], [B, Da]
+  const float* wa_t; const float* pre_t; float* h1t;   // target critic block: [K H] rows
+  int B;
+};
+hipError_t launch_ens_select(const EnsSelectArgs& a, hipStream_t s);
+
+// Phase 2, per (row, policy): the post-step critics on (obs, a_p) from their
+// saved obs projection, the one-hot seed -1/B at the delta_index-th sorted
+// critic k*, da_p through that critic's hidden segment and action columns,
+// dhead_p = da_p (1 - a_p^2) | 0, and the block-diagonal heads' dX
+// dh1[r, p H + j] = [h1[r, p H + j] > 0] sum_d dhead_p[d] wh[p, d, j].
+struct EnsSeedArgs {
+  EnsNets n;
+  const float* act;                     // [B, P, Da]
+  const float* pre;                     // [B, K H] post-step critics' projection of obs (+ bias)
+  const float* h1;                      // [B, P H]
+  float* dhead; float* dh1;             // [B, P, 2 Da], [B, P H]
+  float* ub1; float* ub_last;           // [B, P] every policy's UB; [B] policy P-1's (QNEW)
+  int B;
+};
+hipError_t launch_ens_seed(const EnsSeedArgs& a, hipStream_t s);
+
+// The block-diagonal heads' dW = dhead_p^T h1_p and db = sum_r dhead_p, summed
+// over the rows in four fixed phases, into slab 0 of `S` gradient slabs (the
+// others get zeros: the group's Adam sums every slab).
+struct EnsHeadDwArgs {
+  const float* dhead; const float* h1;  // [B, P, 2 Da], [B, P H]
+  float* gw; float* gb;                 // [P, 2 Da, H], [P, 2 Da] in slab 0
+  long slab_stride; int S;
+  int B, P, H, Da;
+};
+hipError_t launch_ens_head_dw(const EnsHeadDwArgs& a, hipStream_t s);
+
+// oac_ensemble_eval: one workgroup per observation runs layer 0 of the P
+// policies and of the K critics (into LDS), then the step's selection.
+struct EnsEvalArgs {
+  EnsNets n;
+  const float* w0p; const float* b0p;   // stacked policy layer 0 [P H, Do], [P H]
+  const float* w0q; const float* b0q;   // stacked critic layer 0 [K H, Do + Da], [K H]
+  const float* obs; long ld_obs; int Do, N;
+  const float* noise;                   // [N, P, Da] or null
+  int* chosen; float* ub;               // [N], [N, P]
+  float* action; float* mean; float* log_std; float* log_prob; float* std_out; float* pre_tanh;
+};
+size_t ens_eval_lds_bytes(const EnsEvalArgs& a);
+hipError_t launch_ens_eval(const EnsEvalArgs& a, hipStream_t s);
+
 struct DetHeadBwdArgs {                 // d tanh(mean): dmean = da (1 - a^2), d log std = 0
   const float* da[2]; const float* act[2]; float* dhead[2];
   int nseg, B, act_dim;

@@ -83,6 +83,25 @@ static void compute_layout(const oac_sac_config& c, oac_sac_layout& L) {
   L.targets_total = L.n_critics * L.q_size;
 }
 
+// Policy ensemble (oac_sac_create_ensemble): P stacked policies take the place
+// of the policy block in front of [target_policy | critic block]; the pol_*
+// offsets keep a single policy's shape (the target_policy block's).
+static void ensemble_layout(const oac_sac_config& c, int P, oac_sac_layout& L, oac_ensemble_layout& E) {
+  const int64_t Do = c.obs_dim, Da = c.act_dim, H = c.hidden;
+  int64_t o = 0;
+  E.n_policies = P;
+  E.ens_fc0_w = o; o = al4(o + P * H * Do);
+  E.ens_fc0_b = o; o = al4(o + P * H);
+  E.ens_head_w = o; o = al4(o + P * 2 * Da * H);
+  E.ens_head_b = o; o = al4(o + P * 2 * Da);
+  E.ens_size = o;
+  E.tpol_fc0_w = L.pol_fc0_w; E.tpol_fc0_b = L.pol_fc0_b;
+  E.tpol_head_w = L.pol_head_w; E.tpol_head_b = L.pol_head_b; E.tpol_size = L.pol_size;
+  L.tpol_base = E.ens_size;
+  L.q1_base = E.ens_size + L.pol_size;
+  L.params_total = L.q1_base + L.q_size;
+}
+
 // ----------------------------------------------------------------- kinds
 static int own_buffers(int which) { return which; }
 
@@ -388,18 +407,90 @@ static void plan_splits(SacPlan& p) {
   p.S_p = std::max(std::max(p.sp_p0.S, p.sp_p1.S), p.sp_ph.S);
 }
 
-int oac_sac_query_layout(const oac_sac_config* cfg, oac_sac_layout* out) {
-  if (validate(cfg)) return 1;
-  SacPlan p;
-  p.c = *cfg;
-  compute_layout(p.c, p.L);
-  plan_splits(p);
-  kind_ops(p.c.kind).layout(p);
-  *out = p.L;
+// The ensemble entry points' own conditions (P != 0), each by field and kind,
+// ahead of the shared validation.
+static int validate_ensemble(const oac_sac_config* c, int P, const oac_sac_buffers* bufs) {
+  if (!c) { set_error("null config"); return 1; }
+  const char* nm = (c->kind >= 0 && c->kind < kNumKinds) ? kKindNames[c->kind] : "?";
+  if (c->kind != OAC_KIND_PARTICLE_UB) {
+    set_error("ensemble: kind %d (%s) is not supported; the policy ensemble is implemented for "
+              "PARTICLE_UB (kind %d)", c->kind, nm, OAC_KIND_PARTICLE_UB);
+    return 1;
+  }
+  if (P < 1 || P > 16) {
+    set_error("ensemble (kind %d, %s): n_policies must be in 1..16, got %d", c->kind, nm, P);
+    return 1;
+  }
+  if (c->unshared != 1) {
+    set_error("ensemble (kind %d, %s): unshared must be 1 (separate critics; the shared-layer "
+              "ensemble is not implemented), got %d", c->kind, nm, c->unshared);
+    return 1;
+  }
+  if (c->n_hidden != 1) {
+    set_error("ensemble (kind %d, %s): n_hidden must be 1 (one hidden layer), got %d", c->kind, nm,
+              c->n_hidden);
+    return 1;
+  }
+  if (c->world_size != 1) {
+    set_error("ensemble (kind %d, %s): world_size must be 1 (single process), got %d", c->kind, nm,
+              c->world_size);
+    return 1;
+  }
+  if (c->global_opt) {
+    set_error("ensemble (kind %d, %s): global_opt must be 0, got %d", c->kind, nm, c->global_opt);
+    return 1;
+  }
+  if (c->hidden & 3) {
+    set_error("ensemble (kind %d, %s): hidden must be a multiple of 4, got %d", c->kind, nm, c->hidden);
+    return 1;
+  }
+  if (bufs && bufs->next_policy) {
+    set_error("ensemble (kind %d, %s): buffers.next_policy must be NULL (use_target_policy without "
+              "mean_update has no ensemble form)", c->kind, nm);
+    return 1;
+  }
   return 0;
 }
 
+static int query_layout(const oac_sac_config* cfg, int P, oac_sac_layout* out, oac_ensemble_layout* ens) {
+  if (P != 0 && validate_ensemble(cfg, P, nullptr)) return 1;
+  if (validate(cfg)) return 1;
+  if (!out) { set_error("null layout"); return 1; }
+  SacPlan p;
+  p.c = *cfg;
+  compute_layout(p.c, p.L);
+  p.n_policies = P;
+  if (P) ensemble_layout(p.c, P, p.L, p.E);
+  plan_splits(p);
+  kind_ops(p.c.kind).layout(p);
+  *out = p.L;
+  if (ens) *ens = p.E;
+  return 0;
+}
+
+int oac_sac_query_layout(const oac_sac_config* cfg, oac_sac_layout* out) {
+  return query_layout(cfg, 0, out, nullptr);
+}
+
+int oac_sac_query_layout_ensemble(const oac_sac_config* cfg, int n_policies, oac_sac_layout* out,
+                                  oac_ensemble_layout* ens) {
+  if (!ens) { set_error("null ensemble layout"); return 1; }
+  return query_layout(cfg, n_policies, out, ens);
+}
+
+static int create(const oac_sac_config* cfg, int P, const oac_sac_buffers* bufs, oac_sac** out);
+
 int oac_sac_create(const oac_sac_config* cfg, const oac_sac_buffers* bufs, oac_sac** out) {
+  return create(cfg, 0, bufs, out);
+}
+
+int oac_sac_create_ensemble(const oac_sac_config* cfg, int n_policies, const oac_sac_buffers* bufs,
+                            oac_sac** out) {
+  return create(cfg, n_policies, bufs, out);
+}
+
+static int create(const oac_sac_config* cfg, int P, const oac_sac_buffers* bufs, oac_sac** out) {
+  if (P != 0 && validate_ensemble(cfg, P, bufs)) return 1;
   if (validate(cfg)) return 1;
   if (cfg->act_dim > 32) {   // rows.hip: one half-wave lane per action dim
     set_error("the gradient step takes act_dim <= 32, got %d (the parameter layout, exploration "
@@ -411,6 +502,8 @@ int oac_sac_create(const oac_sac_config* cfg, const oac_sac_buffers* bufs, oac_s
   SacPlan& p = h->plan;
   p.c = *cfg;
   compute_layout(p.c, p.L);
+  p.n_policies = P;
+  if (P) ensemble_layout(p.c, P, p.L, p.E);
   plan_splits(p);
   if (p.c.kind == OAC_KIND_SAC_SHALLOW && p.cfg != 0) {   // (sac_shallow_plan.hip: small kernels only)
     set_error("SAC_SHALLOW (kind %d): batch %d with gemm_cfg %d selects the large-batch kernel set "
@@ -466,6 +559,11 @@ int oac_sac_step_n(oac_sac* h, int flags, int n_steps, void* stream) {
   if (p.c.global_opt && (flags & OAC_STEP_USE_GRAPH)) {
     set_error("global_opt (kind %d): OAC_STEP_USE_GRAPH is not supported, issue the step's launches "
               "directly", p.c.kind);
+    return 1;
+  }
+  if (p.n_policies && (flags & OAC_STEP_USE_GRAPH)) {
+    set_error("ensemble (kind %d, n_policies %d): OAC_STEP_USE_GRAPH is not supported, issue the "
+              "step's launches directly", p.c.kind, p.n_policies);
     return 1;
   }
   if (p.c.unshared && (flags & OAC_STEP_USE_GRAPH)) {
@@ -671,6 +769,11 @@ int oac_sac_step_phase(oac_sac* h, int phase, int flags, void* stream) {
     set_error("oac_sac_step_phase: a global_opt handle (kind %d) is single-process", h->plan.c.kind);
     return 1;
   }
+  if (h->plan.n_policies) {
+    set_error("oac_sac_step_phase: an ensemble handle (kind %d, n_policies %d) is single-process",
+              h->plan.c.kind, h->plan.n_policies);
+    return 1;
+  }
   if (h->plan.c.unshared) {
     set_error("oac_sac_step_phase: an unshared handle (kind %d) is single-process", h->plan.c.kind);
     return 1;
@@ -684,6 +787,11 @@ int oac_sac_set_allreduce(oac_sac* h, oac_allreduce_fn fn, void* ctx, int flags)
   if (no_dp_step(p, "oac_sac_set_allreduce")) return 1;
   if (p.c.global_opt) {
     set_error("oac_sac_set_allreduce: a global_opt handle (kind %d) is single-process", p.c.kind);
+    return 1;
+  }
+  if (p.n_policies) {
+    set_error("oac_sac_set_allreduce: an ensemble handle (kind %d, n_policies %d) is single-process",
+              p.c.kind, p.n_policies);
     return 1;
   }
   if (p.c.unshared) {
@@ -757,6 +865,22 @@ int oac_sac_workspace_view(oac_sac* h, int which, int64_t* offset, int64_t* rows
   *offset = w.off; *rows = w.rows; *cols = w.cols;
   if (which == OAC_WS_BATCH || which == OAC_WS_EPS1 || which == OAC_WS_EPS2)
     *rows = h->plan.c.batch;   // slot 0: the batch / eps of a single-step call
+  return 0;
+}
+
+int oac_sac_ensemble_view(oac_sac* h, int which, int64_t* offset, int64_t* rows, int64_t* cols) {
+  if (!h || !offset || !rows || !cols) { set_error("oac_sac_ensemble_view: null argument"); return 1; }
+  if (!h->plan.n_policies) {
+    set_error("oac_sac_ensemble_view: the handle (kind %d) was not created with "
+              "oac_sac_create_ensemble", h->plan.c.kind);
+    return 1;
+  }
+  if (which < 0 || which >= OAC_ENS_VIEW_COUNT) {
+    set_error("oac_sac_ensemble_view: bad view id %d", which);
+    return 1;
+  }
+  const WsBuf& w = h->plan.ws[det_ens_view(which)];
+  *offset = w.off; *rows = w.rows; *cols = w.cols;
   return 0;
 }
 

@@ -22,6 +22,10 @@ struct SacPlan : PlanBase {
   oac_sac_config c;
   oac_sac_layout L;
   oac_sac_buffers b;
+  // policy ensemble (oac_sac_create_ensemble; 0: none): P stacked policies in
+  // front of the target_policy block (E: the stacked block's offsets)
+  int n_policies = 0;
+  oac_ensemble_layout E = {};
   WsBuf ws[kMaxWs];
   Split sp_q0, sp_q1, sp_ql, sp_p0, sp_p1, sp_ph;
   int S_q = 1, S_p = 1;   // slab counts per group (max over the group's dW tasks)
@@ -483,6 +487,7 @@ int particle_ws_alias(int which);
 void det_layout_workspace(SacPlan& p);
 int det_run_step(SacPlan& p, int flags, hipStream_t s, int i, int n);
 int det_step_phase(SacPlan& p, int phase, int flags, hipStream_t s);
+int det_ens_view(int which);   // oac_ens_view -> the det layout's buffer
 // one iteration of the global_opt sweep (rows: the iteration's device index slot, or null =
 // rows 0..N-1 of the replay in place)
 int det_policy_opt_iter(SacPlan& p, const int* rows, StepState* opt, float* hist, hipStream_t s);

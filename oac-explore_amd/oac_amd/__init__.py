@@ -4,7 +4,8 @@ Drop-in replacements for the reference's hot-path interfaces:
   SACTrainer                         trainer/trainer.py (--num_layers 2)
   ShallowSACTrainer                  trainer/trainer.py at one hidden layer (--num_layers 1)
   ParticleTrainer                    trainer/particle_trainer.py (p-oac recipes; share_layers,
-                                     or separate critics at one hidden layer)
+                                     or separate critics at one hidden layer, there
+                                     also ensemble=True: n_policies policies, best-of-P acting)
   ParticleTrainerOAC                 trainer/particle_trainer_oac.py (share_layers)
   GaussianTrainer                    trainer/gaussian_trainer.py (g-oac; share_layers, or
                                      separate q / std critics at one hidden layer)
@@ -26,5 +27,5 @@ from .replay_buffer import (ReplayBuffer, ReplayBufferCount, ReplayBufferNoResam
 from .optimistic_exploration import (get_optimistic_exploration_action,  # noqa: F401
                                      get_optimistic_exploration_actions)
 from .producers import get_policy_producer, get_q_producer  # noqa: F401
-from .networks import MakeDeterministic  # noqa: F401
+from .networks import ArenaEnsemblePolicy, MakeDeterministic  # noqa: F401
 from .rollout import vec_rollout  # noqa: F401

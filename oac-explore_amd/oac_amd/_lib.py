@@ -131,6 +131,18 @@ class SacLayout(ctypes.Structure):
         "tpol_base")]
 
 
+class EnsembleLayout(ctypes.Structure):
+    """oac_ensemble_layout: the stacked policy block of a policy ensemble and
+    the target_policy block's single-policy offsets."""
+    _fields_ = [(n, ctypes.c_int64) for n in (
+        "n_policies", "ens_fc0_w", "ens_fc0_b", "ens_head_w", "ens_head_b", "ens_size",
+        "tpol_fc0_w", "tpol_fc0_b", "tpol_head_w", "tpol_head_b", "tpol_size")]
+
+
+# enum oac_ens_view
+ENS_VIEWS = {name: i for i, name in enumerate(["sel", "ub_next", "act", "head", "ub_obs"])}
+
+
 class SacBuffers(ctypes.Structure):
     _fields_ = [
         ("params", ctypes.c_void_p), ("grads", ctypes.c_void_p), ("adam_m", ctypes.c_void_p),
@@ -152,6 +164,21 @@ _SIGS = {
     "oac_sac_query_layout": (ctypes.c_int, [ctypes.POINTER(SacConfig), ctypes.POINTER(SacLayout)]),
     "oac_sac_create": (ctypes.c_int, [ctypes.POINTER(SacConfig), ctypes.POINTER(SacBuffers),
                                       ctypes.POINTER(ctypes.c_void_p)]),
+    "oac_sac_query_layout_ensemble": (ctypes.c_int, [ctypes.POINTER(SacConfig), ctypes.c_int,
+                                                     ctypes.POINTER(SacLayout),
+                                                     ctypes.POINTER(EnsembleLayout)]),
+    "oac_sac_create_ensemble": (ctypes.c_int, [ctypes.POINTER(SacConfig), ctypes.c_int,
+                                               ctypes.POINTER(SacBuffers),
+                                               ctypes.POINTER(ctypes.c_void_p)]),
+    "oac_sac_ensemble_view": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int,
+                                             ctypes.POINTER(ctypes.c_int64),
+                                             ctypes.POINTER(ctypes.c_int64),
+                                             ctypes.POINTER(ctypes.c_int64)]),
+    "oac_ensemble_eval": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+                                         ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                         ctypes.c_void_p, ctypes.c_int64, ctypes.c_int] +
+                          [ctypes.c_void_p] * 10),
     "oac_sac_destroy": (ctypes.c_int, [ctypes.c_void_p]),
     "oac_sac_step": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
     "oac_sac_step_n": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int,

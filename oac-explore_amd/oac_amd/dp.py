@@ -134,6 +134,10 @@ class _DataParallel:
             raise NotImplementedError(
                 "the data-parallel trainers do not implement global_opt (the policy sweep, "
                 "optimize_policies, is single-process); unsupported: ['global_opt']")
+        if kwargs.get("ensemble"):
+            raise NotImplementedError(
+                "the data-parallel trainers do not implement ensemble (the policy ensemble's "
+                "step is single-process); unsupported: ['ensemble']")
         if isinstance(self, (ParticleTrainer, GaussianTrainer)) and not kwargs.get("share_layers"):
             raise NotImplementedError(
                 "the data-parallel trainers do not implement share_layers=False (separate "

@@ -245,6 +245,133 @@ class ArenaTanhGaussianPolicy(nn.Module):
         pass
 
 
+class _SliceLayout:
+    """The pol_* offsets of policy ``p`` inside a stacked policy block
+    (oac_ensemble_layout): slice p of each stacked tensor, one hidden layer."""
+
+    def __init__(self, E, p, obs_dim, act_dim, hidden):
+        self.pol_fc0_w = int(E.ens_fc0_w) + p * hidden * obs_dim
+        self.pol_fc0_b = int(E.ens_fc0_b) + p * hidden
+        self.pol_fc1_w = self.pol_fc1_b = -1
+        self.pol_head_w = int(E.ens_head_w) + p * 2 * act_dim * hidden
+        self.pol_head_b = int(E.ens_head_b) + p * 2 * act_dim
+
+
+class ArenaEnsemblePolicy:
+    """EnsemblePolicy (trainer/policies.py:546-647) without share_layers, over
+    the trainer's stacked policy block: ``policies`` are P
+    ``ArenaTanhGaussianPolicy`` views of slice p, and acting picks, per
+    observation, the proposal with the largest upper bound of the critics
+    (``approximator.predict``), the first maximum winning.  ``forward``,
+    ``get_action`` and ``get_best_actions`` run the P policies, the K critics
+    and the choice in ONE oac_ensemble_eval launch on torch's current stream
+    (no host synchronisation); the chosen indices of the last such call stay on
+    the device in ``last_choice`` and the proposals' upper bounds in
+    ``last_upper_bounds`` [N, P].  A sampled call draws one [N, P, Da] normal
+    tensor (``noise=`` fixes it): every policy samples, as the reference's loop
+    over ``policies`` does."""
+
+    share_layers = False
+
+    def __init__(self, arena, ens_layout, obs_dim, act_dim, hidden, approximator):
+        E = ens_layout
+        self.n_policies = int(E.n_policies)
+        self.policies = [ArenaTanhGaussianPolicy(arena, 0, _SliceLayout(E, p, obs_dim, act_dim, hidden),
+                                                 obs_dim, act_dim, hidden)
+                         for p in range(self.n_policies)]
+        self.approximator = approximator
+        self.arena = arena
+        self.obs_dim, self.action_dim, self.hidden = obs_dim, act_dim, hidden
+        self.input_size, self.output_size = obs_dim, act_dim
+        self._offs = (ctypes.c_int64 * 4)(int(E.ens_fc0_w), int(E.ens_fc0_b), int(E.ens_head_w),
+                                          int(E.ens_head_b))
+        self.last_choice = self.last_upper_bounds = None
+        self.oac_trainer = None
+
+    def __call__(self, *args, **kwargs):
+        return self.forward(*args, **kwargs)
+
+    def _eval(self, obs, sample, noise=None, log_prob=False):
+        """One oac_ensemble_eval call on x [N, Do]: dict of device tensors."""
+        tr = self.approximator
+        dev = self.arena.device
+        x = _as_input(obs, dev)
+        if torch.is_grad_enabled() and x.requires_grad:
+            raise NotImplementedError("oac_amd ensemble forward: no gradient w.r.t. the observation "
+                                      "(the gradient step runs in the trainer's plan)")
+        x = x.contiguous()
+        N, Da, P = x.shape[0], self.action_dim, self.n_policies
+        e = lambda *sh: torch.empty(*sh, dtype=torch.float32, device=dev)
+        out = dict(action=e(N, Da), mean=e(N, Da), log_std=e(N, Da), std=e(N, Da), pre_tanh=e(N, Da),
+                   ub=e(N, P), chosen=torch.empty(N, dtype=torch.int32, device=dev))
+        if sample:
+            noise = torch.randn(N, P, Da, device=dev) if noise is None else \
+                _as_input(noise, dev).reshape(N, P, Da).contiguous()
+        else:
+            noise = None
+        out["log_prob"] = e(N) if (sample and log_prob) else None
+        lay = tr.layout
+        qoffs = (ctypes.c_int64 * 4)(int(lay.q_fc0_w), int(lay.q_fc0_b), int(lay.q_last_w),
+                                     int(lay.q_last_b))
+        critics = ctypes.c_void_p(tr.params.data_ptr() + 4 * int(lay.q1_base))
+        _lib.check(_lib.lib().oac_ensemble_eval(
+            _lib.ptr(self.arena), self._offs, P, critics, qoffs, int(tr.num_particles),
+            int(tr.delta_index), self.obs_dim, Da, self.hidden, _lib.ptr(x), self.obs_dim, N,
+            _lib.ptr(noise), _lib.ptr(out["chosen"]), _lib.ptr(out["ub"]), _lib.ptr(out["action"]),
+            _lib.ptr(out["mean"]), _lib.ptr(out["log_std"]), _lib.ptr(out["log_prob"]),
+            _lib.ptr(out["std"]), _lib.ptr(out["pre_tanh"]),
+            _lib.stream_ptr(torch.cuda.current_stream(dev))))
+        self.last_choice, self.last_upper_bounds = out["chosen"], out["ub"]
+        return out
+
+    def forward(self, obs, reparameterize=True, deterministic=False, return_log_prob=False,
+                noise=None):
+        """policies.py:576-606: the chosen policy's 6-tuple per row."""
+        x = _as_input(obs, self.arena.device)
+        one = x.dim() == 1
+        o = self._eval(x[None] if one else x, not deterministic, noise, return_log_prob)
+        action, mean, pre = o["action"], o["mean"], o["pre_tanh"]
+        if o["log_prob"] is not None:
+            log_prob = o["log_prob"].view(-1, 1)
+        else:
+            log_prob = torch.zeros_like(action)
+            pre = mean
+        out = (action, mean, o["log_std"], log_prob, o["std"], pre)
+        return tuple(t[0] for t in out) if one else out
+
+    @torch.no_grad()
+    def get_best_actions(self, obs_np, deterministic=False, noise=None):
+        """The chosen action of each of N observations [N, Da] (numpy), one
+        launch for all of them (no reference counterpart; vec_rollout uses it)."""
+        obs = torch.as_tensor(np.asarray(obs_np), dtype=torch.float32, device=self.arena.device)
+        return self._eval(obs, not deterministic, noise)["action"].cpu().numpy()
+
+    def get_action(self, obs_np, deterministic=False):
+        """policies.py:608-631."""
+        return self.get_best_actions(np.asarray(obs_np)[None], deterministic=deterministic)[0, :], {}
+
+    def get_actions(self, obs_np, deterministic=False, index=0):
+        """policies.py:633-634: policy ``index`` alone."""
+        return self.policies[index].get_actions(obs_np, deterministic=deterministic)
+
+    def reset(self):
+        pass
+
+    def load_state_dict(self, state_dicts):
+        for i, pol in enumerate(self.policies):
+            pol.load_state_dict(state_dicts[i])
+
+    def state_dict(self, **args):
+        return [pol.state_dict(**args) for pol in self.policies]
+
+    def to(self, **args):
+        """policies.py:649-651 (the arena stays where the trainer put it)."""
+        dev = args.get("device")
+        if dev is not None and torch.device(dev) != self.arena.device:
+            raise NotImplementedError("oac_amd ensemble policy: the parameters live in the trainer's "
+                                      "arena and cannot move to another device")
+
+
 class MakeDeterministic(nn.Module):
     """Evaluation wrapper (trainer/policies.py:486-513)."""
 

@@ -14,6 +14,15 @@ the interface is the reference's: constructor kwargs, ``train`` /
 ``train_from_torch``, ``predict``, ``obj_func``, ``get_diagnostics``,
 ``end_epoch``, ``networks``, ``get_snapshot`` / ``restore_from_snapshot``,
 ``qfs`` / ``tfs`` / ``qf_optimizers`` / ``target_policy``.
+
+``ensemble=True, n_policies=P`` (main.py's ``--ensemble``; with separate critics
+at one hidden layer, 1 <= P <= 16: w_oac_mountain_no_resampling.sh): P
+separately optimised policies, stored stacked; the TD target's next action is
+the best of the P proposals under the online critics' upper bound, policy p
+ascends its own upper bound, and ``policy`` is an ``ArenaEnsemblePolicy`` that
+acts the same way (particle_trainer.py:115-137, 203-206, 321-338;
+``policy_optimizers``, the reference's ``networks``, statistics and snapshot
+keys).
 """
 from collections import OrderedDict
 
@@ -37,7 +46,17 @@ class ParticleTrainer(_TargetPolicyTrainer):
                  std_soft_update_prob=0., train_bias=True, use_target_policy=False,
                  rescale_targets_around_mean=False,
                  device=None, seed=0, use_graph=False, gemm_cfg=-1):
-        unsupported = dict(deterministic=not deterministic, ensemble=ensemble)
+        unsupported = dict(deterministic=not deterministic)
+        if ensemble:
+            # the policy ensemble (particle_trainer.py:115-137) runs with separate
+            # critics at one hidden layer, as direct launches on one process; the
+            # options it does not take, every one by name
+            unsupported.update(
+                share_layers=share_layers, global_opt=global_opt, use_graph=use_graph,
+                mellow_max=mellow_max,
+                # (the reference's constructor fails here: soft_update_from_to of an EnsemblePolicy)
+                use_target_policy=use_target_policy and not mean_update,
+                n_policies=not (isinstance(n_policies, (int, np.integer)) and 1 <= n_policies <= 16))
         bad = [k for k, v in unsupported.items() if v]
         if bad:
             raise NotImplementedError(
@@ -45,7 +64,10 @@ class ParticleTrainer(_TargetPolicyTrainer):
                 "(share_layers=True, or one critic per particle at one hidden layer; "
                 "deterministic policy, counts / std_soft_update / "
                 "mean_update / rescale_targets_around_mean / train_bias / "
-                f"use_target_policy, global_opt, no ensemble); unsupported: {bad}")
+                "use_target_policy, global_opt; ensemble=True with 1 <= n_policies <= 16 for "
+                "share_layers=False at one hidden layer, without global_opt / use_graph / "
+                "mellow_max, and use_target_policy only with mean_update); "
+                f"unsupported: {bad if not ensemble else ['ensemble'] + bad}")
         assert not counts or not std_soft_update   # particle_trainer.py:92
         self._common_init(device, soft_target_tau, target_update_period, deterministic,
                           discount, reward_scale, policy_lr, qf_lr, use_graph, seed, gemm_cfg)
@@ -98,6 +120,23 @@ class ParticleTrainer(_TargetPolicyTrainer):
         else:
             ref_q = q_producer(bias=init_values, train_bias=train_bias)
             q_producer(bias=init_values, train_bias=train_bias)
+        if ensemble:
+            # particle_trainer.py:117-127: each policy starts biased at an initial
+            # action.  Da > 1 draws P Da values on numpy's global stream and
+            # EnsemblePolicy uses the first P of them, one per policy, filled into
+            # every action dimension (policies.py:569, 224-225) -- kept as it is.
+            if action_space.shape[0] > 1:
+                initial_actions = np.random.uniform(
+                    low=action_space.low, high=action_space.high,
+                    size=(n_policies, action_space.shape[0])).flatten()
+            else:
+                initial_actions = np.linspace(-1., 1., n_policies)
+                initial_actions[0] += 5e-2
+                initial_actions[-1] -= 5e-2
+            self.initial_actions = initial_actions
+            ref_pol = policy_producer(bias=initial_actions, ensemble=ensemble,
+                                      n_policies=n_policies, approximator=self,
+                                      share_layers=share_layers)
         ref_init = policy_producer() if global_opt else None
         ref_tp = policy_producer()
         ref_init_tp = policy_producer() if global_opt else None

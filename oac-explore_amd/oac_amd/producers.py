@@ -43,9 +43,36 @@ class InitMlp(nn.Module):
                 self.last_fc_log_std.bias.uniform_(-init_w, init_w)
 
 
+class InitEnsemble:
+    """What ``policy_producer(ensemble=True, ...)`` returns: ``policies``, the
+    n_policies networks of an EnsemblePolicy without share_layers
+    (trainer/policies.py:567-570), policy i built with ``bias[i]``."""
+
+    def __init__(self, policies, approximator=None):
+        self.policies, self.n_policies = policies, len(policies)
+        self.share_layers, self.approximator = False, approximator
+
+    def state_dict(self, **kw):
+        return [p.state_dict(**kw) for p in self.policies]
+
+
 def get_policy_producer(obs_dim, action_dim, hidden_sizes, device=None):
-    def policy_producer(**kwargs):
-        return InitMlp(obs_dim, hidden_sizes, action_dim, 1e-3, log_std_head=True, device=device)
+    def make(bias=None):
+        # TanhGaussianPolicy (policies.py:224-225): the mean head's bias is
+        # arctanh(bias), a scalar filled into every action dimension
+        if bias is not None:
+            bias = np.full(action_dim, np.arctanh(bias), np.float64)
+        return InitMlp(obs_dim, hidden_sizes, action_dim, 1e-3, log_std_head=True, bias=bias,
+                       device=device)
+
+    def policy_producer(bias=None, ensemble=False, n_policies=1, approximator=None,
+                        share_layers=False, **kwargs):
+        if not ensemble:
+            return make()
+        if share_layers:
+            raise NotImplementedError("oac_amd.producers: the shared-layer policy ensemble is not "
+                                      "implemented; unsupported: ['ensemble', 'share_layers']")
+        return InitEnsemble([make(bias[i]) for i in range(n_policies)], approximator)
     return policy_producer
 
 

@@ -56,7 +56,11 @@ def _batch_actions(agent, obs, optimistic_exploration, kwargs, deterministic_pol
         kw.pop("deterministic", None)
         A, _ = get_optimistic_exploration_actions(obs, eps=eps, **kw)
         return A, [{} for _ in range(n)]
-    if hasattr(agent, "stochastic_policy"):          # MakeDeterministic (policies.py:486-513)
+    if hasattr(agent, "get_best_actions"):           # policy ensemble: the best of P proposals per
+        A = agent.get_best_actions(obs, deterministic=deterministic_pol)   # row, one launch
+    elif hasattr(getattr(agent, "stochastic_policy", None), "get_best_actions"):
+        A = agent.stochastic_policy.get_best_actions(obs, deterministic=True)   # MakeDeterministic(ensemble)
+    elif hasattr(agent, "stochastic_policy"):        # MakeDeterministic (policies.py:486-513)
         A = agent.get_actions(obs)
     else:
         A = agent.get_actions(obs, deterministic=deterministic_pol)

@@ -21,7 +21,7 @@ import torch
 
 from . import _lib
 from ._lib import check, stream_ptr
-from .networks import ArenaFlattenMlp, ArenaTanhGaussianPolicy
+from .networks import ArenaEnsemblePolicy, ArenaFlattenMlp, ArenaTanhGaussianPolicy
 from .trainer import AdamStateView, _ArenaTrainer, _dims_from_state, _twin_views, _plain_stats
 
 _LOG_STD_HEAD = ("last_fc_log_std.weight", "last_fc_log_std.bias")
@@ -57,6 +57,8 @@ class _TargetPolicyTrainer(_ArenaTrainer):
         self.use_graph, self.seed, self._gemm_cfg = use_graph, int(seed), gemm_cfg
 
     unshared = False        # share_layers=False: separate one-output critics (oac_sac_config.unshared)
+    ensemble = False        # ParticleTrainer(ensemble=True): n_policies stacked policies
+    n_policies = 1
     std_lr = 0.0
 
     def _reject_unshared_options(self):
@@ -75,9 +77,18 @@ class _TargetPolicyTrainer(_ArenaTrainer):
         ``qf_lr`` / ``positives`` / ``frozen`` are lists over the K one-output
         critics, stored stacked in one critic block (include/oac_amd.h), each
         exposed through modules and an optimizer view of its own slices."""
-        pol_sd = {k: v.detach() for k, v in ref_pol.state_dict().items()}
+        ens = list(ref_pol.policies) if self.ensemble else None   # EnsemblePolicy, or any .policies
+        if ens is not None and len(ens) != self.n_policies:
+            raise ValueError(f"ensemble: policy_producer built {len(ens)} policies, "
+                             f"n_policies={self.n_policies}")
+        pol_sd = {k: v.detach() for k, v in (ens[0] if ens else ref_pol).state_dict().items()}
         q0 = ref_q[0] if self.unshared else ref_q
         Do, Da, H, K, self.n_hidden = _dims_from_state(pol_sd, q0.state_dict(), depths=(1, 2))
+        if ens is not None and self.n_hidden != 1:
+            raise NotImplementedError(
+                f"oac_amd.{type(self).__name__}: ensemble=True is implemented for one hidden layer "
+                f"(--num_layers 1, the w_oac recipe); got {self.n_hidden} hidden layers; "
+                f"unsupported: ['ensemble', 'num_layers']")
         if self.unshared and self.n_hidden != 1:
             raise NotImplementedError(
                 f"oac_amd.{type(self).__name__}: share_layers=False is implemented for one hidden "
@@ -91,10 +102,18 @@ class _TargetPolicyTrainer(_ArenaTrainer):
         if not self.unshared and K != self._q_out:
             raise ValueError(f"share_layers: q_producer must build a critic with {self._q_out} "
                              f"outputs, got {K}")
+        self._ens_policies = self.n_policies if ens is not None else 0
         lay = self._alloc(Do, Da, H, self.device)
-        self.policy = ArenaTanhGaussianPolicy(self.params, 0, lay, Do, Da, H)
+        if ens is not None:
+            # the P policies stacked in front of the target_policy block
+            # (oac_ensemble_layout); `policy` acts as the reference's EnsemblePolicy
+            self.policy = ArenaEnsemblePolicy(self.params, self.ens_layout, Do, Da, H, self)
+            self.policy.load_state_dict(
+                [{k: v.detach() for k, v in m.state_dict().items()} for m in ens])
+        else:
+            self.policy = ArenaTanhGaussianPolicy(self.params, 0, lay, Do, Da, H)
+            self.policy.load_state_dict(pol_sd)
         self.target_policy = ArenaTanhGaussianPolicy(self.params, lay.tpol_base, lay, Do, Da, H)
-        self.policy.load_state_dict(pol_sd)
         self.target_policy.load_state_dict({k: v.detach() for k, v in ref_tp.state_dict().items()})
         self.policy.oac_trainer = self
         if self.unshared:
@@ -116,7 +135,7 @@ class _TargetPolicyTrainer(_ArenaTrainer):
             tf.load_state_dict({k: v.detach() for k, v in ref_qt.state_dict().items()})
             self.qfs, self.tfs = [qf], [tf]
         tw = lambda other, mod: _twin_views(self.params, other, list(mod.parameters()))
-        names = [n for n, _ in self.policy.named_parameters()]
+        names = [n for n, _ in (self.policy.policies[0] if ens else self.policy).named_parameters()]
         # deterministic policies: the log-std heads never get a gradient
         no_grad = [i for i, n in enumerate(names) if n in _LOG_STD_HEAD]
 
@@ -127,8 +146,17 @@ class _TargetPolicyTrainer(_ArenaTrainer):
         # global_opt: the policy's optimizer is stepped by optimize_policies
         # alone (utils/core.py:98), so its `step` counts sweep iterations
         self._policy_opt_steps = 0
-        self.policy_optimizer = popt(
-            self.policy, (lambda: self._policy_opt_steps) if self.global_opt else None)
+        if ens is not None:
+            # particle_trainer.py:128-137: one Adam per policy, all stepped once per
+            # train step; SACTrainer's policy_optimizer stays, over the discarded
+            # parent policy, and is never stepped (no state; a snapshot key only)
+            self.policy_optimizers = [popt(pol) for pol in self.policy.policies]
+            self.policy_optimizer = AdamStateView(
+                self, list(self.policy.policies[0].parameters()), [], [], policy_lr, (0.9, 0.999),
+                1e-8, step_source=lambda: 0)
+        else:
+            self.policy_optimizer = popt(
+                self.policy, (lambda: self._policy_opt_steps) if self.global_opt else None)
         self.target_policy_optimizer = popt(self.target_policy)
         self.qf_optimizers = []
         for k, qf in enumerate(self.qfs):
@@ -254,6 +282,8 @@ class _TargetPolicyTrainer(_ArenaTrainer):
         the previous iteration; 'none': rows 0..N-1 every iteration, no host
         work.  ``policy_opt_history`` = {'loss', 'grad_norm'} per iteration,
         read back once at the end."""
+        if self.ensemble:   # particle_trainer.py:519-520
+            return None
         if not self.global_opt:
             raise RuntimeError("optimize_policies needs a trainer built with global_opt=True")
         if save_fig:
@@ -321,7 +351,9 @@ class _TargetPolicyTrainer(_ArenaTrainer):
 
     @property
     def networks(self):
-        nets = [self.policy] + self.qfs + self.tfs + [self.target_policy]
+        # (particle_trainer.py:437-445: an ensemble lists its P policies)
+        pols = list(self.policy.policies) if self.ensemble else [self.policy]
+        nets = pols + self.qfs + self.tfs + [self.target_policy]
         if getattr(self, "target_policy_network", None) is not None:
             nets.append(self.target_policy_network)
         return nets
@@ -342,12 +374,21 @@ class _TargetPolicyTrainer(_ArenaTrainer):
                     target_policy_opt_state_dict=self.target_policy_optimizer.state_dict())
         if getattr(self, "target_policy_network", None) is not None:
             d["target_policy_network"] = self.target_policy_network.state_dict()
+        if self.ensemble:
+            # policy_state_dict is the list of P state dicts and policy_optim_state_dict
+            # the never-stepped parent optimizer, as the reference writes them; the P
+            # optimizers it leaves out are an extra key
+            d["policy_optims_state_dicts"] = [o.state_dict() for o in self.policy_optimizers]
         return d
 
     def restore_from_snapshot(self, ss):
         """gaussian_trainer.py:484-517 / particle_trainer.py:480-505."""
         self.policy.load_state_dict(ss["policy_state_dict"])
         self.policy_optimizer.load_state_dict(ss["policy_optim_state_dict"])
+        if self.ensemble and "policy_optims_state_dicts" in ss:
+            # (a reference-written snapshot has no such key: the moments stay as they are)
+            for opt, sd in zip(self.policy_optimizers, ss["policy_optims_state_dicts"]):
+                opt.load_state_dict(sd)
         if self.global_opt:   # the policy optimizer's own step count, back into the device counter
             steps = [int(v["step"]) for v in ss["policy_optim_state_dict"]["state"].values()]
             self._set_policy_opt_steps(max(steps) if steps else 0)

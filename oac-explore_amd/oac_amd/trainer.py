@@ -156,13 +156,26 @@ class _ArenaTrainer(object):
     _q_out = 1
     n_hidden = 2   # hidden layers of the policy and the critic (1: the det trainers, ShallowSACTrainer)
 
+    _ens_policies = 0   # policy ensemble (ParticleTrainer ensemble=True): n_policies, else 0
+
+    def _query_layout(self, cfg):
+        """oac_sac_layout of ``cfg`` -- through the ensemble entry point (which
+        also fills ``ens_layout``) for a trainer with a policy ensemble."""
+        L, lay = _lib.lib(), _lib.SacLayout()
+        if self._ens_policies:
+            ens = _lib.EnsembleLayout()
+            check(L.oac_sac_query_layout_ensemble(ctypes.byref(cfg), int(self._ens_policies),
+                                                  ctypes.byref(lay), ctypes.byref(ens)))
+            self.ens_layout = ens
+        else:
+            check(L.oac_sac_query_layout(ctypes.byref(cfg), ctypes.byref(lay)))
+        return lay
+
     def _alloc(self, Do, Da, H, device):
-        L = _lib.lib()
         self.obs_dim, self.act_dim, self.hidden = Do, Da, H
         self.rows = row_layout(Do, Da)
         cfg = self._make_cfg(1)
-        lay = _lib.SacLayout()
-        check(L.oac_sac_query_layout(ctypes.byref(cfg), ctypes.byref(lay)))
+        lay = self._query_layout(cfg)
         self.layout = lay
         z = lambda n: torch.zeros(int(n), dtype=torch.float32, device=device)
         self.params, self.grads = z(lay.params_total), z(lay.params_total)
@@ -223,8 +236,7 @@ class _ArenaTrainer(object):
             return p
         L = _lib.lib()
         cfg = self._make_cfg(B)
-        lay = _lib.SacLayout()
-        check(L.oac_sac_query_layout(ctypes.byref(cfg), ctypes.byref(lay)))
+        lay = self._query_layout(cfg)
         ws = torch.zeros(int(lay.workspace_floats), dtype=torch.float32, device=self.device)
         bufs = _lib.SacBuffers()
         bufs.params, bufs.grads = self.params.data_ptr(), self.grads.data_ptr()
@@ -240,8 +252,19 @@ class _ArenaTrainer(object):
             bufs.counts, bufs.count_tags, bufs.count_epoch = (t.data_ptr() for t in count_state)
         bufs.next_policy = self._next_policy_ptr()
         h = ctypes.c_void_p()
-        check(L.oac_sac_create(ctypes.byref(cfg), ctypes.byref(bufs), ctypes.byref(h)))
+        if self._ens_policies:
+            check(L.oac_sac_create_ensemble(ctypes.byref(cfg), int(self._ens_policies),
+                                            ctypes.byref(bufs), ctypes.byref(h)))
+        else:
+            check(L.oac_sac_create(ctypes.byref(cfg), ctypes.byref(bufs), ctypes.byref(h)))
         views = {}
+        if self._ens_policies:   # the selection's and the P policies' row values (oac_ens_view)
+            for name, wid in _lib.ENS_VIEWS.items():
+                off, r, c = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
+                check(L.oac_sac_ensemble_view(h, wid, ctypes.byref(off), ctypes.byref(r),
+                                              ctypes.byref(c)))
+                views["ens_" + name] = ws[off.value:off.value + r.value * c.value].view(
+                    r.value, c.value)
         for name, wid in _lib.WS.items():
             off, r, c = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
             rc = L.oac_sac_workspace_view(h, wid, ctypes.byref(off), ctypes.byref(r),
